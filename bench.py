@@ -565,6 +565,36 @@ class Scratch:
         self.bufs = None
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much over all ranks
+
+
+def last_step_outputs(last, mode):
+    """Device copies of what the last step of the region just timed returned to its caller: obs [N, obs_dim], reward, done,
+    success [N]."""
+    if mode == "step":
+        obs, rew, done, succ = last["step"]
+    else:
+        out, row = last["rollout"]
+        obs, rew, done, succ = (out[k][row] for k in ("obs", "reward", "done", "success"))
+    return {"obs": obs.clone(), "reward": rew.clone(), "done": done.clone(), "success": succ.clone()}
+
+
+def dump_outputs(path, outs, rank, world, n):
+    """--dump-outputs: every array as float32 <path>/<name>.npy (<name>.rank<r>.npy for world > 1).  If the rank's share of
+    DUMP_BYTES cannot hold all n envs, the same seeded sample of env rows is kept on every run, with its global env ids."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in outs.items()}
+    row_bytes = sum(a[0].nbytes for a in arrs.values()) + 8
+    keep = (DUMP_BYTES // world) // row_bytes
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["env_index"] = (idx + rank * n).astype(np.float64)
+    sfx = ".rank%d" % rank if world > 1 else ""
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + sfx + ".npy"), a)
+
+
 def self_launch(n_ranks, argv):
     """`python bench.py --gpus N` without a launcher around it (how the round driver types it): start the N ranks here, one
     per GPU, as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>
@@ -654,6 +684,10 @@ def main():
     ap.add_argument("--mode", default="rollout", choices=["rollout", "step"])
     ap.add_argument("--rollout-steps", type=int, default=100,
                     help="env steps fused per armenv_rollout launch (default: the reference's logging period, main.py:130)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, write what the last step of the contract's timed region returned to its caller -- obs, reward, "
+                         "done, success of every env of the rank -- as DIR/<name>.npy (float32; ranks > 1: <name>.rank<r>.npy); above "
+                         "%d MB in all, a fixed sample of envs (numpy default_rng(0)) and its global env ids as env_index.npy" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
 
     from armenv import envs
@@ -718,6 +752,7 @@ def main():
     R = min(R, S)
     bufs = {}
     cursor = [0]     # next row of the action pool
+    last = {}        # where the last step of the most recently planned region leaves its outputs (--dump-outputs)
 
     def next_actions(r):
         """r consecutive rows of the pool as a contiguous view (wraps to row 0 when fewer than r are left)"""
@@ -746,7 +781,10 @@ def main():
         if args.mode == "step":
             for i in range(k):
                 a = next_actions(1)[0]
-                ops.append(lambda a=a: env.step(a))
+                if i == k - 1:       # the tensors env.step returns are the same every call: keep the last call's
+                    ops.append(lambda a=a: last.__setitem__("step", env.step(a)))
+                else:
+                    ops.append(lambda a=a: env.step(a))
                 if multi and (i + 1) % args.gather_every == 0:
                     ops.append(do_gather); gathers += 1
         else:
@@ -754,9 +792,10 @@ def main():
             while done_steps < k:
                 r = min(R, k - done_steps)
                 a_in = None if args.policy != "external" else next_actions(r)
-                launch, _ = env.bind_rollout(r, a_in, out=bufs if r == R else None)
+                launch, out_ = env.bind_rollout(r, a_in, out=bufs if r == R else None)
                 ops.append(launch)
                 done_steps += r
+                last["rollout"] = (out_, r - 1)
                 if multi and (done_steps // args.gather_every) != ((done_steps - r) // args.gather_every):
                     ops.append(do_gather); gathers += 1
         if multi and ops and ops[-1] is do_gather:
@@ -886,6 +925,8 @@ def main():
     if snap is not None and os.environ.get("ARMENV_BENCH_RESTORE_FIRST") == "1":
         env.set_state(**snap, sync=False)       # diagnostic: the contract region behind the same (idempotent) restore as its repeats
     wall, gpu_ms, launches, gathers, dc, wall_steps = timed(args.steps, tag="r0", ahead_ms=args.busy_ahead_ms)
+    # device copies, after the clock: the repeats below write into the same buffers
+    dumped = last_step_outputs(last, args.mode) if args.dump_outputs else None
     host_us_main = dict(host_us)
     extra_main = dict(extra)
 
@@ -1144,6 +1185,8 @@ def main():
             cfg["cpu_env_steps_per_s"] = line["cpu_baseline"]["value"]
             cfg["cpu_cores"] = line["cpu_baseline"]["cores"]
         print(json.dumps(line), flush=True)
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, rank, world, n)
     env.close()
     gather.close()
     shm.close()

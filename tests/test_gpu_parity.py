@@ -2414,6 +2414,33 @@ def test_bench_line_contract():
     assert d["value_steps"] >= d["value"] >= 0.9 * d["value_steps"] and d["value_bracketed"] > 0
 
 
+@pytest.mark.parametrize("mode", ["rollout", "step"])
+def test_bench_dump_outputs_are_the_last_timed_step(envs, mode, tmp_path):
+    """`--dump-outputs DIR`: obs / reward / done / success of the last of the K timed steps, as float32 .npy files, equal bit for bit
+    to the same seeded trajectory driven on a handle of its own (env seed 0, the action pool of Generator(1000), W warm-up
+    steps first) -- whatever the launch shape; `--steps` is the number of timed steps and `ms_per_step` their wall time per step."""
+    n, K, W = 4096, 30, 5
+    out = tmp_path / "dump"
+    d = _run_bench(["--steps", str(K), "--warmup", str(W), "--envs-per-gpu", str(n), "--mode", mode, "--prewarm-ms", "0",
+                    "--repeat-regions", "0", "--fence-steps", "0", "--large-batch", "0", "--secondary-legs", "0", "--no-cpu-baseline",
+                    "--dump-outputs", str(out)])
+    assert d["steps"] == K and d["warmup"] == W and d["ms_per_step"] > 0 and d["config"]["mode"] == mode
+    assert abs(d["value"] - n * K / (d["ms_per_step"] * K / 1e3)) / d["value"] < 1e-6
+    assert sorted(os.listdir(out)) == ["done.npy", "obs.npy", "reward.npy", "success.npy"]
+    got = {k: np.load(out / (k + ".npy")) for k in ("obs", "reward", "done", "success")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    gen = torch.Generator(device=DEV); gen.manual_seed(1000)
+    pool = (torch.randn((1000, n, 3), device=DEV, generator=gen) * 0.686).clamp_(-0.7, 0.7)
+    e = _mk(envs, n, seed=0)
+    e.reset()
+    e.rollout(W, pool[:W].contiguous())
+    o = e.rollout(K, pool[W:W + K].contiguous())
+    want = {"obs": o["obs"][-1], "reward": o["reward"][-1], "done": o["done"][-1], "success": o["success"][-1]}
+    for k, v in want.items():
+        assert np.array_equal(got[k], _np(v).astype(np.float32)), k
+    e.close()
+
+
 def test_bench_two_ranks_on_one_gpu_shard_the_trajectory(envs):
     """`bench.py --gpus 2` under torch.distributed.run on this one GPU (the ranks share it, so the logging collective falls
     back to gloo): the multi-rank control flow of BASELINE config 5 -- env-index sharding, barriers, max-over-ranks timing,
@@ -2496,14 +2523,15 @@ def test_bench_plain_python_launches_its_own_ranks():
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
 
 
-def test_bench_eight_ranks_on_one_gpu_config5_control_flow(envs):
-    """BASELINE configs[4] -- rl_reach_env sharded across 8 ranks, an all-gather of episode returns -- at world = 8 on this ONE
-    GPU (the ranks share it, the logging collective falls back to gloo; on an 8-GPU node the same command runs one rank per GPU
-    over RCCL): env_id_offset up to 7 x N, the 8-way gather inside the timed region, max-over-ranks timing.  The eight shard
-    digests equal the eight slices of ONE 8 x N-env handle, and the gathered vector of episode returns equals that handle's
-    armenv_episode_stats."""
+def test_bench_four_ranks_on_one_gpu_config5_control_flow(envs):
+    """BASELINE configs[4] -- rl_reach_env sharded across ranks, an all-gather of episode returns -- at world = 4 on this ONE
+    GPU (the ranks share it, the logging collective falls back to gloo; on an 8-GPU node `--gpus 8` runs one rank per GPU
+    over RCCL): env_id_offset up to 3 x N, the 4-way gather inside the timed region, max-over-ranks timing.  The four shard
+    digests equal the four slices of ONE 4 x N-env handle, and the gathered vector of episode returns equals that handle's
+    armenv_episode_stats.  Four ranks, their torch.distributed.run launcher (it queries the device) and this test's own
+    process are six processes holding the one device: the most a shared GPU node admits at once."""
     import hashlib
-    n, K, W, world = 8192, 700, 5, 8          # 700 steps: every env finishes its first 501-step episode, so the returns are live
+    n, K, W, world = 8192, 700, 5, 4          # 700 steps: every env finishes its first 501-step episode, so the returns are live
     d = _run_bench(["--gpus", str(world), "--steps", str(K), "--warmup", str(W), "--envs-per-gpu", str(n), "--state-digest",
                     "--prewarm-ms", "0", "--gather-every", "100"], nproc=world, timeout=1200)
     assert d["n_gpus"] == world and d["config"]["total_envs"] == world * n and d["config"]["gathers_in_timed_region"] >= 7

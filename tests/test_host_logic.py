@@ -316,6 +316,36 @@ def test_capture_safe_linear_is_linear():
     assert abs(float(mean_sq(d)) - float(F.mse_loss(d, torch.zeros_like(d)))) < 1e-15 and abs(float(neg_mean(d)) + float(d.mean())) < 1e-15
 
 
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 files; above the byte budget a seeded sample of env rows -- the same rows on every run
+    -- with their global env ids (rank r of a multi-rank job owns ids r*N .. r*N+N-1 and writes <name>.rank<r>.npy)."""
+    import torch
+    import bench
+    n = 1000
+    outs = {"obs": torch.arange(n * 6, dtype=torch.float32).reshape(n, 6), "reward": torch.arange(n, dtype=torch.float32),
+            "done": torch.arange(n) % 3 == 0, "success": torch.arange(n) % 5 == 0}
+    bench.dump_outputs(str(tmp_path / "all"), outs, 0, 1, n)
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in outs}
+    assert sorted(os.listdir(tmp_path / "all")) == ["done.npy", "obs.npy", "reward.npy", "success.npy"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    for k, v in outs.items():
+        assert np.array_equal(got[k], v.numpy().astype(np.float32)), k
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 44 * 100)           # 100 rows per rank at 2 ranks (9 floats + 1 id per row)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), outs, 1, 2, n)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(k + ".rank1.npy" for k in list(outs) + ["env_index"])
+    total = 0
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(a, b) and a.shape[0] == 100 and a.dtype in (np.float32, np.float64)
+        total += a.nbytes
+    assert total <= 2 * 44 * 100 // 2
+    ids = np.load(tmp_path / "a" / "env_index.rank1.npy")
+    assert (np.diff(ids) > 0).all() and ids.min() >= n and ids.max() < 2 * n
+    assert np.array_equal(np.load(tmp_path / "a" / "reward.rank1.npy"), (ids - n).astype(np.float32))
+
+
 def test_bench_launcher_relays_exit_code_and_refuses_contradictions():
     """`python bench.py --gpus 2` without WORLD_SIZE starts its own two ranks (torch.distributed.run on a free 127.0.0.1 port) and
     relays their exit code -- here, without a GPU, both ranks fail, and the launcher must come back non-zero without a JSON line
