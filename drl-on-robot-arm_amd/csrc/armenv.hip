@@ -16,33 +16,6 @@ int armenv_fail(int code, const char *fmt, ...) {
   return code;
 }
 
-int EngineBase::set_actor(const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
-                          const float *b3, int in_dim, float bound, hipStream_t s) {
-  const size_t n1 = ACTOR_HID * ACTOR_W1P_COLS, n2 = (size_t)ACTOR_HID * ACTOR_HID, n3 = ACTOR_HID * 4;
-  // f32 tables, then the two f16 tables (n2 halfs each = n2 floats together)
-  if (!actor_buf && hipMalloc(reinterpret_cast<void **>(&actor_buf), (n1 + n2 + n3 + n2) * sizeof(float)) != hipSuccess)
-    return fail(ARMENV_ENOMEM, "armenv_set_policy: hipMalloc failed");
-  float *W1P = actor_buf, *W2P = actor_buf + n1, *B2W3 = actor_buf + n1 + n2;
-  _Float16 *W2H = reinterpret_cast<_Float16 *>(actor_buf + n1 + n2 + n3), *W2L = W2H + n2;
-  hipLaunchKernelGGL(actor_pack_kernel, dim3((unsigned)(n2 / 256)), dim3(256), 0, s, W1, b1, W2, b2, W3, in_dim, W1P, W2P, B2W3,
-                     W2H, W2L, 3);
-  pol.actor_h.W2H = reinterpret_cast<const half8 *>(W2H);
-  pol.actor_h.W2L = reinterpret_cast<const half8 *>(W2L);
-  HIP_TRY(hipGetLastError());
-  float hb3[3];
-  HIP_TRY(hipMemcpyAsync(hb3, b3, sizeof hb3, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  pol.actor.W1P = W1P;
-  pol.actor.W2P = reinterpret_cast<const float4 *>(W2P);
-  pol.actor.B2W3 = reinterpret_cast<const float4 *>(B2W3);
-  for (int k = 0; k < 3; ++k) pol.actor.b3[k] = hb3[k];
-  pol.actor.bound = bound;
-  pol.actor.in_dim = in_dim;
-  pol.actor.raw = 0;
-  pol.actor.lds_image = nullptr;
-  return ARMENV_OK;
-}
-
 // DATD3_MLP.take_action (/root/reference/algo/DATD3/DATD3_mlp.py:88-109) for n reach states (6 floats): actions [n][3], and (nullable)
 // the two Q values and which actor was picked.
 template <int OBS>
@@ -74,13 +47,46 @@ static __global__ __launch_bounds__(256) void actor_lds_image_kernel(const float
   for (int i = threadIdx.x; i < ACTOR_W1_LDS_FLOATS_H / 4; i += blockDim.x) image[i] = tab[i];
 }
 
+// One 256-wide MLP packed into `base` for the device: W1P | W2P | B2W3 | W2H + W2L [| LDS image], described by A and H.
+// in_dim: the columns of m.W1; rows: the rows of m.W3 (3: PolicyNet, 1: QValueNet); raw: A.raw.  image_dim > 0: the net runs as
+// an image_dim-input net (W1P's zero columns behind in_dim) and the LDS tables for it are built once behind W2L (lds_image).
+int EngineBase::pack_net(const ArmEnvMlp &m, int in_dim, int rows, bool raw, int image_dim, float bound, float *base,
+                         ActorParams &A, ActorParamsH &H, hipStream_t s) {
+  float *W1P = base, *W2P = base + kNetW2P, *B2W3 = base + kNetB2W3;
+  _Float16 *W2H = reinterpret_cast<_Float16 *>(base + kNetW2H), *W2L = W2H + kNetW2;
+  float4 *image = image_dim > 0 ? reinterpret_cast<float4 *>(base + kNetImage) : nullptr;
+  hipLaunchKernelGGL(actor_pack_kernel, dim3((unsigned)(kNetW2 / 256)), dim3(256), 0, s, m.W1, m.b1, m.W2, m.b2, m.W3, in_dim, W1P,
+                     W2P, B2W3, W2H, W2L, rows);
+  if (image)
+    hipLaunchKernelGGL(actor_lds_image_kernel, dim3(1), dim3(256), 0, s, W1P, reinterpret_cast<const float4 *>(B2W3), image, image_dim);
+  HIP_TRY(hipGetLastError());
+  float hb3[3] = {0.f, 0.f, 0.f};
+  HIP_TRY(hipMemcpyAsync(hb3, m.b3, sizeof(float) * rows, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  A.W1P = W1P;
+  A.W2P = reinterpret_cast<const float4 *>(W2P);
+  A.B2W3 = reinterpret_cast<const float4 *>(B2W3);
+  for (int k = 0; k < 3; ++k) A.b3[k] = hb3[k];
+  A.bound = bound;
+  A.in_dim = image ? image_dim : in_dim;
+  A.raw = raw ? 1 : 0;
+  A.lds_image = image;
+  H.W2H = reinterpret_cast<const half8 *>(W2H);
+  H.W2L = reinterpret_cast<const half8 *>(W2L);
+  return ARMENV_OK;
+}
+
+int EngineBase::set_actor(const ArmEnvMlp &m, int in_dim, float bound, hipStream_t s) {
+  if (!actor_buf && hipMalloc(reinterpret_cast<void **>(&actor_buf), kNetImage * sizeof(float)) != hipSuccess)
+    return fail(ARMENV_ENOMEM, "armenv_set_policy: hipMalloc failed");
+  return pack_net(m, in_dim, 3, false, 0, bound, actor_buf, pol.actor, pol.actor_h, s);
+}
+
 // armenv_set_policy_datd3: the four nets packed like set_actor packs one (the W2P table of the exact-f32 actor is not needed: the
 // fused DATD3 policy runs the f16x3 passes only), every net as an (obs_dim + 3)-input net (datd3_forward_wg): the actors' W1 rows carry
 // zeros in the three columns behind obs_dim, the critics' W1 is [hidden][obs_dim + 3] as it is.
 int EngineBase::set_datd3(const ArmEnvMlp *const nets[4], int obs_dim, float bound, hipStream_t s) {
-  const size_t n1 = ACTOR_HID * ACTOR_W1P_COLS, n2 = (size_t)ACTOR_HID * ACTOR_HID, n3 = ACTOR_HID * 4;
-  const size_t n4 = ACTOR_W1_LDS_FLOATS_H;                       // the LDS table image
-  const size_t per_net = n1 + n2 + n3 + n2 + n4;                 // floats: W1P | W2P (unused scratch of the packer) | B2W3 | W2H + W2L | image
+  const size_t per_net = kNetImage + ACTOR_W1_LDS_FLOATS_H;
   const size_t tab = (4 * sizeof(ActorParams) + 4 * sizeof(ActorParamsH) + sizeof(float) - 1) / sizeof(float);
   if (!datd3_buf && hipMalloc(reinterpret_cast<void **>(&datd3_buf), (4 * per_net + tab) * sizeof(float)) != hipSuccess)
     return fail(ARMENV_ENOMEM, "armenv_set_policy_datd3: hipMalloc failed");
@@ -97,27 +103,9 @@ int EngineBase::set_datd3(const ArmEnvMlp *const nets[4], int obs_dim, float bou
       H[3] = H[2];
       continue;
     }
-    float *base = datd3_buf + k * per_net;
-    float *W1P = base, *W2P = base + n1, *B2W3 = base + n1 + n2;
-    _Float16 *W2H = reinterpret_cast<_Float16 *>(base + n1 + n2 + n3), *W2L = W2H + n2;
-    hipLaunchKernelGGL(actor_pack_kernel, dim3((unsigned)(n2 / 256)), dim3(256), 0, s, m.W1, m.b1, m.W2, m.b2, m.W3,
-                       critic ? obs_dim + 3 : obs_dim, W1P, W2P, B2W3, W2H, W2L, critic ? 1 : 3);
-    float4 *image = reinterpret_cast<float4 *>(base + n1 + n2 + n3 + n2);
-    hipLaunchKernelGGL(actor_lds_image_kernel, dim3(1), dim3(256), 0, s, W1P, reinterpret_cast<const float4 *>(B2W3), image, obs_dim + 3);
-    HIP_TRY(hipGetLastError());
-    float hb3[3] = {0.f, 0.f, 0.f};
-    HIP_TRY(hipMemcpyAsync(hb3, m.b3, sizeof(float) * (critic ? 1 : 3), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    A[k].W1P = W1P;
-    A[k].W2P = reinterpret_cast<const float4 *>(W2P);
-    A[k].B2W3 = reinterpret_cast<const float4 *>(B2W3);
-    for (int j = 0; j < 3; ++j) A[k].b3[j] = hb3[j];
-    A[k].bound = bound;
-    A[k].in_dim = obs_dim + 3;
-    A[k].raw = critic ? 1 : 0;
-    A[k].lds_image = image;
-    H[k].W2H = reinterpret_cast<const half8 *>(W2H);
-    H[k].W2L = reinterpret_cast<const half8 *>(W2L);
+    const int rc = pack_net(m, critic ? obs_dim + 3 : obs_dim, critic ? 1 : 3, critic, obs_dim + 3, bound, datd3_buf + k * per_net,
+                            A[k], H[k], s);
+    if (rc != ARMENV_OK) return rc;
   }
   char *t = reinterpret_cast<char *>(datd3_buf + 4 * per_net);
   HIP_TRY(hipMemcpyAsync(t, A, sizeof A, hipMemcpyHostToDevice, s));
@@ -129,25 +117,30 @@ int EngineBase::set_datd3(const ArmEnvMlp *const nets[4], int obs_dim, float bou
   return ARMENV_OK;
 }
 
+// f(std::integral_constant<int, 6 | 9>): a net's observation width (reach | push, pick) as a template argument
+template <class F> static void with_obs(int obs_dim, F &&f) {
+  if (obs_dim == 6) f(std::integral_constant<int, 6>{});
+  else f(std::integral_constant<int, 9>{});
+}
+
 int EngineBase::datd3_forward(int64_t n, const float *states, float *actions, float *q1, float *q2, uint8_t *picked, hipStream_t s) {
   if (!pol.datd3) return fail(ARMENV_ESTATE, "armenv_datd3_forward: no DATD3 policy installed (armenv_set_policy_datd3)");
-  if (datd3_obs == 6) hipLaunchKernelGGL(datd3_kernel<6>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pol.datd3, pol.datd3_h, n, states, actions, q1, q2, picked);
-  else hipLaunchKernelGGL(datd3_kernel<9>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pol.datd3, pol.datd3_h, n, states, actions, q1, q2, picked);
+  with_obs(datd3_obs, [&](auto obs) {
+    hipLaunchKernelGGL(datd3_kernel<decltype(obs)::value>, dim3(grid_for(n, 256)), dim3(256), 0, s, pol.datd3, pol.datd3_h, n, states,
+                       actions, q1, q2, picked);
+  });
   HIP_TRY(hipGetLastError());
   return ARMENV_OK;
 }
 
 int EngineBase::actor_forward(int64_t n, const float *states, float *actions, hipStream_t s) {
   if (!pol.actor.W2P) return fail(ARMENV_ESTATE, "armenv_actor_forward: no actor installed (armenv_set_policy)");
-  const unsigned grid = (unsigned)((n + 255) / 256);
   const bool fast = pol.kind == ARMENV_POLICY_ACTOR_F16X3;
-  if (pol.actor.in_dim == 6) {
-    if (fast) hipLaunchKernelGGL((actor_kernel<6, 1>), dim3(grid), dim3(256), 0, s, pol.actor, pol.actor_h, n, states, actions);
-    else hipLaunchKernelGGL((actor_kernel<6, 0>), dim3(grid), dim3(256), 0, s, pol.actor, pol.actor_h, n, states, actions);
-  } else {
-    if (fast) hipLaunchKernelGGL((actor_kernel<9, 1>), dim3(grid), dim3(256), 0, s, pol.actor, pol.actor_h, n, states, actions);
-    else hipLaunchKernelGGL((actor_kernel<9, 0>), dim3(grid), dim3(256), 0, s, pol.actor, pol.actor_h, n, states, actions);
-  }
+  with_obs(pol.actor.in_dim, [&](auto obs) {
+    constexpr int D = decltype(obs)::value;
+    if (fast) hipLaunchKernelGGL((actor_kernel<D, 1>), dim3(grid_for(n, 256)), dim3(256), 0, s, pol.actor, pol.actor_h, n, states, actions);
+    else hipLaunchKernelGGL((actor_kernel<D, 0>), dim3(grid_for(n, 256)), dim3(256), 0, s, pol.actor, pol.actor_h, n, states, actions);
+  });
   HIP_TRY(hipGetLastError());
   return ARMENV_OK;
 }
@@ -251,6 +244,28 @@ __global__ __launch_bounds__(256) void clock_probe_kernel(unsigned long long *ou
     row[0] = w1 - w0; row[1] = c1 - c0; row[2] = w0;
     row[3] = (unsigned long long)(xcc & 15u) | ((unsigned long long)CLOCK_PROBE_CHAIN << 8) | (x == 12345.f ? 1ull << 63 : 0ull);
   }
+}
+
+// What armenv_set_policy and armenv_set_policy_datd3 share: the noise check, the checks of a fused policy (`pack` then installs its
+// nets) and the policy itself.  fn, nets_are, need64, book: the caller's wording of the errors.
+template <class Pack>
+static int install_policy(ArmEnv *env, int32_t kind, int32_t hidden_dim, float action_bound, float noise_sigma, float noise_clip,
+                          const char *fn, const char *nets_are, const char *need64, const char *book, Pack &&pack) {
+  if (kind != ARMENV_POLICY_EXTERNAL && !(noise_sigma >= 0.f && noise_clip > 0.f))
+    return fail(ARMENV_EINVAL, "%s: need noise_sigma >= 0 and noise_clip > 0", fn);
+  if (fused_policy(kind)) {
+    if (hidden_dim != ACTOR_HID)
+      return fail(ARMENV_EINVAL, "%s: hidden_dim %d; the fused %s built for %d (config.py:56)", fn, hidden_dim, nets_are, ACTOR_HID);
+    if (env->cfg.num_envs % 64 != 0) return fail(ARMENV_EINVAL, "%s: %s", fn, need64);
+    if (env->cfg.fence_counters) return fail(ARMENV_ESTATE, "%s: %s", fn, book);
+    const int rc = pack();
+    if (rc != ARMENV_OK) return rc;
+  }
+  env->eng->pol.kind = kind;
+  env->eng->pol.sigma = noise_sigma;
+  env->eng->pol.clip = noise_clip;
+  env->eng->pol.bound = action_bound;
+  return ARMENV_OK;
 }
 
 extern "C" {
@@ -437,8 +452,7 @@ int armenv_step(ArmEnv *env, const float *action_dev, float *obs_dev, float *rew
     return fail(ARMENV_ESTATE, "armenv_step: ik_updates_dev needs a handle created with fence_counters >= 1 (the bookkeeping build of the kernels)");
   if (diag_dev && env->cfg.fence_counters != 2)
     return fail(ARMENV_ESTATE, "armenv_step: diag_dev needs a handle created with fence_counters = 2");
-  if (diag_dev && !action_dev && (env->eng->pol.kind == ARMENV_POLICY_ACTOR || env->eng->pol.kind == ARMENV_POLICY_ACTOR_F16X3 || env->eng->pol.kind == ARMENV_POLICY_DATD3 ||
-      env->eng->pol.kind == ARMENV_POLICY_DADDPG))
+  if (diag_dev && !action_dev && fused_policy(env->eng->pol.kind))
     return fail(ARMENV_ESTATE, "armenv_step: diag_dev is not available with a fused actor");
   StepIO io{action_dev, obs_dev, reward_dev, done_dev, success_dev, terminal_obs_dev, ik_updates_dev, diag_dev};
   if (!action_dev) {   // fused policy: a one-step rollout
@@ -511,26 +525,14 @@ int armenv_set_policy(ArmEnv *env, int32_t policy, const float *W1_dev, const fl
   ENV_ENTER(env);
   if (policy < ARMENV_POLICY_EXTERNAL || policy > ARMENV_POLICY_ACTOR_F16X3)
     return fail(ARMENV_EINVAL, "armenv_set_policy: unknown policy %d", policy);
-  if (policy != ARMENV_POLICY_EXTERNAL && !(noise_sigma >= 0.f && noise_clip > 0.f))
-    return fail(ARMENV_EINVAL, "armenv_set_policy: need noise_sigma >= 0 and noise_clip > 0");
-  if (policy == ARMENV_POLICY_ACTOR || policy == ARMENV_POLICY_ACTOR_F16X3) {
-    if (!W1_dev || !b1_dev || !W2_dev || !b2_dev || !W3_dev || !b3_dev) return fail(ARMENV_EINVAL, "armenv_set_policy: NULL weight pointer");
-    if (hidden_dim != ACTOR_HID)
-      return fail(ARMENV_EINVAL, "armenv_set_policy: hidden_dim %d; the fused actor is built for %d (config.py:56)", hidden_dim, ACTOR_HID);
-    if (env->cfg.num_envs % 64 != 0)
-      return fail(ARMENV_EINVAL, "armenv_set_policy: the fused actor needs num_envs to be a multiple of 64 (full wavefronts)");
-    if (env->cfg.fence_counters)
-      return fail(ARMENV_ESTATE, "armenv_set_policy: the bookkeeping builds of the kernels (fence_counters, ik_tip_offset) exist for external "
-                                 "actions and the in-kernel random policy, not for the fused actors");
-    const int rc = env->eng->set_actor(W1_dev, b1_dev, W2_dev, b2_dev, W3_dev, b3_dev, armenv_obs_dim(env), action_bound,
-                                       static_cast<hipStream_t>(stream));
-    if (rc != ARMENV_OK) return rc;
-  }
-  env->eng->pol.kind = policy;
-  env->eng->pol.sigma = noise_sigma;
-  env->eng->pol.clip = noise_clip;
-  env->eng->pol.bound = action_bound;
-  return ARMENV_OK;
+  if (fused_policy(policy) && (!W1_dev || !b1_dev || !W2_dev || !b2_dev || !W3_dev || !b3_dev))
+    return fail(ARMENV_EINVAL, "armenv_set_policy: NULL weight pointer");
+  const ArmEnvMlp m{W1_dev, b1_dev, W2_dev, b2_dev, W3_dev, b3_dev};
+  return install_policy(env, policy, hidden_dim, action_bound, noise_sigma, noise_clip, "armenv_set_policy", "actor is",
+                        "the fused actor needs num_envs to be a multiple of 64 (full wavefronts)",
+                        "the bookkeeping builds of the kernels (fence_counters, ik_tip_offset) exist for external "
+                        "actions and the in-kernel random policy, not for the fused actors",
+                        [&] { return env->eng->set_actor(m, armenv_obs_dim(env), action_bound, static_cast<hipStream_t>(stream)); });
 }
 
 int armenv_set_policy_datd3(ArmEnv *env, const ArmEnvMlp *actor1, const ArmEnvMlp *actor2, const ArmEnvMlp *critic1,
@@ -540,19 +542,10 @@ int armenv_set_policy_datd3(ArmEnv *env, const ArmEnvMlp *actor1, const ArmEnvMl
   const ArmEnvMlp *nets[4] = {actor1, actor2, critic1, critic2};
   for (const ArmEnvMlp *m : nets)
     if (!m || !m->W1 || !m->b1 || !m->W2 || !m->b2 || !m->W3 || !m->b3) return fail(ARMENV_EINVAL, "armenv_set_policy_datd3: NULL network or weight pointer");
-  if (!(noise_sigma >= 0.f && noise_clip > 0.f)) return fail(ARMENV_EINVAL, "armenv_set_policy_datd3: need noise_sigma >= 0 and noise_clip > 0");
-  if (hidden_dim != ACTOR_HID)
-    return fail(ARMENV_EINVAL, "armenv_set_policy_datd3: hidden_dim %d; the fused nets are built for %d (config.py:56)", hidden_dim, ACTOR_HID);
-  if (env->cfg.num_envs % 64 != 0) return fail(ARMENV_EINVAL, "armenv_set_policy_datd3: num_envs must be a multiple of 64 (full wavefronts)");
-  if (env->cfg.fence_counters)
-    return fail(ARMENV_ESTATE, "armenv_set_policy_datd3: not on a bookkeeping handle (fence_counters, ik_tip_offset)");
-  const int rc = env->eng->set_datd3(nets, armenv_obs_dim(env), action_bound, static_cast<hipStream_t>(stream));
-  if (rc != ARMENV_OK) return rc;
-  env->eng->pol.kind = ARMENV_POLICY_DATD3;
-  env->eng->pol.sigma = noise_sigma;
-  env->eng->pol.clip = noise_clip;
-  env->eng->pol.bound = action_bound;
-  return ARMENV_OK;
+  return install_policy(env, ARMENV_POLICY_DATD3, hidden_dim, action_bound, noise_sigma, noise_clip, "armenv_set_policy_datd3", "nets are",
+                        "num_envs must be a multiple of 64 (full wavefronts)",
+                        "not on a bookkeeping handle (fence_counters, ik_tip_offset)",
+                        [&] { return env->eng->set_datd3(nets, armenv_obs_dim(env), action_bound, static_cast<hipStream_t>(stream)); });
 }
 
 int armenv_set_policy_daddpg(ArmEnv *env, const ArmEnvMlp *actor1, const ArmEnvMlp *actor2, const ArmEnvMlp *critic, int32_t hidden_dim,
@@ -591,8 +584,7 @@ int armenv_rollout(ArmEnv *env, int32_t steps, const float *actions_dev, float *
     return fail(ARMENV_ESTATE, "armenv_rollout: ik_updates_dev needs a handle created with fence_counters >= 1 (the bookkeeping build of the kernels)");
   if (diag_dev && env->cfg.fence_counters != 2)
     return fail(ARMENV_ESTATE, "armenv_rollout: diag_dev needs a handle created with fence_counters = 2");
-  if ((ik_updates_dev || diag_dev) && !actions_dev && (env->eng->pol.kind == ARMENV_POLICY_ACTOR || env->eng->pol.kind == ARMENV_POLICY_ACTOR_F16X3 || env->eng->pol.kind == ARMENV_POLICY_DATD3 ||
-      env->eng->pol.kind == ARMENV_POLICY_DADDPG))
+  if ((ik_updates_dev || diag_dev) && !actions_dev && fused_policy(env->eng->pol.kind))
     return fail(ARMENV_ESTATE, "armenv_rollout: ik_updates_dev / diag_dev are not available with a fused actor");
   StepIO io{nullptr, obs_dev, reward_dev, done_dev, success_dev, terminal_obs_dev, ik_updates_dev, diag_dev};
   return env->eng->rollout(steps, actions_dev, io, actions_out_dev, static_cast<hipStream_t>(stream));

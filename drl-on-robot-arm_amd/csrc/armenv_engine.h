@@ -82,9 +82,13 @@ struct EngineBase {
   virtual int step(const StepIO &io, hipStream_t s) = 0;
   virtual int rollout(int32_t steps, const float *actions, const StepIO &io0, float *actions_out, hipStream_t s) = 0;
   PolicyParams pol{};
-  float *actor_buf = nullptr;   // packed W1P | W2P | B2W3 on the handle's device
-  int set_actor(const float *W1, const float *b1, const float *W2, const float *b2, const float *W3, const float *b3,
-                int in_dim, float bound, hipStream_t s);
+  // float offsets of a packed net (pack_net): W1P | W2P | B2W3 | W2H + W2L (two f16 tables of kNetW2 halfs = kNetW2 floats) | LDS image
+  static constexpr size_t kNetW2 = (size_t)ACTOR_HID * ACTOR_HID, kNetW2P = ACTOR_HID * ACTOR_W1P_COLS, kNetB2W3 = kNetW2P + kNetW2,
+                          kNetW2H = kNetB2W3 + ACTOR_HID * 4, kNetImage = kNetW2H + kNetW2;
+  int pack_net(const ArmEnvMlp &m, int in_dim, int rows, bool raw, int image_dim, float bound, float *base, ActorParams &A,
+               ActorParamsH &H, hipStream_t s);
+  float *actor_buf = nullptr;   // one packed net without an LDS image on the handle's device
+  int set_actor(const ArmEnvMlp &m, int in_dim, float bound, hipStream_t s);
   float *datd3_buf = nullptr;   // four packed nets + the device arrays of their ActorParams / ActorParamsH (armenv_set_policy_datd3)
   int set_datd3(const ArmEnvMlp *const nets[4], int obs_dim, float bound, hipStream_t s);
   int datd3_obs = 0;            // observation width the installed DATD3 nets were packed for (6 | 9)
@@ -105,6 +109,12 @@ struct EngineBase {
 
 static inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
+// the policies whose network runs inside env_rollout_kernel's workgroup phase (DADDPG: the DATD3 kernel over a net table whose two
+// critics are one)
+static constexpr bool fused_policy(int kind) {
+  return kind == ARMENV_POLICY_ACTOR || kind == ARMENV_POLICY_ACTOR_F16X3 || kind == ARMENV_POLICY_DATD3 || kind == ARMENV_POLICY_DADDPG;
+}
+
 
 // One engine per (task, chain, precision); each task x precision pair is compiled in its own translation unit
 // (armenv_task.hip, see the Makefile) so that the kernel variants build in parallel.
@@ -114,8 +124,20 @@ template <template <class, class, int> class LaneT, class C, typename T> struct 
   using LaneTip = LaneT<C, T, 2>; // the bookkeeping build with the IK evaluated at ArmEnvConfig.ik_tip_offset + the f64 step diagnostics
   bool fence_on = false;          // bookkeeping kernels (fence_counters, or implied by a tip offset)
   bool tip_on = false;
-  // run f with the lane type of the handle's bookkeeping build, passed as a null pointer tag
-  template <class F> void with_book_lane(F &&f) { if (tip_on) f((LaneTip *)nullptr); else f((LaneF *)nullptr); }
+  // Run f(lane, waves) with the kernel build to launch: the lane type as a null pointer tag (Lane, or the bookkeeping LaneF /
+  // LaneTip of the handle) and the waves per SIMD as a std::integral_constant (1, or 2 when `two`).  kFused: the fused actors,
+  // which exist as Lane with one wave only -- nothing else is instantiated for them.
+  template <bool kFused = false, class F> void with_build(bool two, F &&f) {
+    auto waves = [&](auto *lane) {
+      if constexpr (!kFused)
+        if (two) return f(lane, std::integral_constant<int, 2>{});
+      f(lane, std::integral_constant<int, 1>{});
+    };
+    if constexpr (kFused) waves((Lane *)nullptr);
+    else if (tip_on) waves((LaneTip *)nullptr);
+    else if (fence_on) waves((LaneF *)nullptr);
+    else waves((Lane *)nullptr);
+  }
   EnvParams<T> P{};
   void *pool = nullptr;
   unsigned long long *counter_totals = nullptr;
@@ -139,11 +161,6 @@ template <template <class, class, int> class LaneT, class C, typename T> struct 
     if (lanes_cfg == 64 || two_waves()) return false;
     if (lanes_cfg == 32) return true;
     return task != ARMENV_TASK_REACH && (P.n + 31) / 32 <= (int64_t)4 * cus;
-  }
-  int lane_block() const {
-    const int64_t waves = half_waves() ? (P.n + 31) / 32 : (P.n + 63) / 64;
-    const int64_t per_cu = (waves + cus - 1) / cus;
-    return 64 * (int)(per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
   }
   static constexpr int task = Lane::kTask;
   std::string kname;
@@ -283,27 +300,6 @@ template <template <class, class, int> class LaneT, class C, typename T> struct 
     HIP_TRY(hipGetLastError());
     return ARMENV_OK;
   }
-  // launch geometry of the kernels without a workgroup phase: threads to cover every env, and the params with the lane mapping
-  int64_t lane_threads(bool half) const { return half ? 64 * ((P.n + 31) / 32) : P.n; }
-  EnvParams<T> params(bool half) const { EnvParams<T> Q = P; Q.half_waves = half ? 1 : 0; return Q; }
-  int step(const StepIO &io, hipStream_t s) override {
-    // the one-launch-per-step kernel keeps full waves: a launch ends with its slowest wave whatever the wave count, and twice
-    // as many waves share the CUs' instruction fetch (push, 32 768 envs: 22.9 us per launch with full waves, 23.4 with half)
-    const bool h = false;
-    const int b = 64 * (int)std::min<int64_t>(4, std::max<int64_t>(1, ((P.n + 63) / 64 + cus - 1) / cus));
-    if (fence_on) {
-      with_book_lane([&](auto *tag) {
-        using LX = std::remove_pointer_t<decltype(tag)>;
-        if (two_waves()) hipLaunchKernelGGL((env_step_kernel<LX, T, 2>), dim3(grid_for(P.n, block)), dim3(block), 0, s, P, io);
-        else hipLaunchKernelGGL((env_step_kernel<LX, T>), dim3(grid_for(lane_threads(h), b)), dim3(b), 0, s, params(h), io);
-      });
-    } else {
-      if (two_waves()) hipLaunchKernelGGL((env_step_kernel<Lane, T, 2>), dim3(grid_for(P.n, block)), dim3(block), 0, s, P, io);
-      else hipLaunchKernelGGL((env_step_kernel<Lane, T>), dim3(grid_for(lane_threads(h), b)), dim3(b), 0, s, params(h), io);
-    }
-    HIP_TRY(hipGetLastError());
-    return ARMENV_OK;
-  }
   // Two waves per SIMD (env_rollout_kernel<..., 2>) when the batch has more waves than the chip has SIMDs, or when the
   // caller asks for it (ArmEnvConfig.rollout_waves_per_simd); never with a fused actor.
   bool two_waves() const {
@@ -311,68 +307,63 @@ template <template <class, class, int> class LaneT, class C, typename T> struct 
     if (waves_cfg == 2) return true;
     return (P.n + 63) / 64 > (int64_t)4 * cus;
   }
-  template <int POLICY, class LaneX = Lane>
-  void launch_rollout(int32_t steps, const float *actions, const StepIO &io0, float *actions_out, hipStream_t s) {
-    constexpr bool kActor = POLICY == ARMENV_POLICY_ACTOR || POLICY == ARMENV_POLICY_ACTOR_F16X3 || POLICY == ARMENV_POLICY_DATD3;
-    if constexpr (!kActor) {
-      if (two_waves()) {
-        hipLaunchKernelGGL((env_rollout_kernel<LaneX, T, POLICY, 2>), dim3(grid_for(P.n, block)), dim3(block), 0, s, P, pol,
-                           steps, actions, io0, actions_out);
-        return;
-      }
-    }
-    const int b = kActor ? block : lane_block();
-    const bool h = !kActor && half_waves();
-    hipLaunchKernelGGL((env_rollout_kernel<LaneX, T, POLICY>), dim3(grid_for(lane_threads(h), b)), dim3(b), 0, s, params(h), pol, steps,
-                       actions, io0, actions_out);
+  // the env kernels by launch geometry: one step per launch, lockstep rollout, lane-asynchronous rollout, and the rollout with a
+  // workgroup phase (the fused actors)
+  enum class Family { Step, Rollout, RolloutAsync, RolloutWg };
+  struct Launch {
+    dim3 grid, block;
+    EnvParams<T> P;   // P with the lane mapping (EnvParams::half_waves)
+    bool two;         // the two-waves-per-SIMD build
+  };
+  Launch geometry(Family f) const {
+    // the fused actors' MFMA phases need full waves and the whole register file: four waves per workgroup, one per SIMD
+    if (f == Family::RolloutWg) return {dim3(grid_for(P.n, block)), dim3(block), P, false};
+    if (two_waves()) return {dim3(grid_for(P.n, block)), dim3(block), P, true};
+    // the one-launch-per-step kernel keeps full waves: a launch ends with its slowest wave whatever the wave count, and twice
+    // as many waves share the CUs' instruction fetch (push, 32 768 envs: 22.9 us per launch with full waves, 23.4 with half)
+    const bool h = f != Family::Step && half_waves();
+    const int64_t waves = h ? (P.n + 31) / 32 : (P.n + 63) / 64, per_cu = (waves + cus - 1) / cus;
+    const int b = 64 * (int)std::min<int64_t>(4, std::max<int64_t>(1, per_cu));
+    EnvParams<T> Q = P;
+    Q.half_waves = h;
+    return {dim3(grid_for(64 * waves, b)), dim3(b), Q, false};
   }
-  template <int POLICY, class LaneX = Lane>
-  void launch_rollout_async(int32_t steps, const float *actions, const StepIO &io0, float *actions_out, hipStream_t s) {
-    if (two_waves()) {
-      hipLaunchKernelGGL((env_rollout_async_kernel<LaneX, T, POLICY, 2>), dim3(grid_for(P.n, block)), dim3(block), 0, s, P, pol,
-                         steps, actions, io0, actions_out, (int32_t)ready_lanes, (int32_t)straggler_trips);
-      return;
-    }
-    const int b = lane_block();
-    const bool h = half_waves();
-    // count rule under half-filled waves: the same share of the live lanes (62 of 64 -> 31 of 32; 22.1 us vs 23.2 at 30)
-    hipLaunchKernelGGL((env_rollout_async_kernel<LaneX, T, POLICY>), dim3(grid_for(lane_threads(h), b)), dim3(b), 0, s, params(h), pol, steps,
-                       actions, io0, actions_out, (int32_t)(h ? (ready_lanes + 1) / 2 : ready_lanes), (int32_t)straggler_trips);
+  int step(const StepIO &io, hipStream_t s) override {
+    const Launch G = geometry(Family::Step);
+    with_build(G.two, [&](auto *lane, auto waves) {
+      using LX = std::remove_pointer_t<decltype(lane)>;
+      hipLaunchKernelGGL((env_step_kernel<LX, T, decltype(waves)::value>), G.grid, G.block, 0, s, G.P, io);
+    });
+    HIP_TRY(hipGetLastError());
+    return ARMENV_OK;
   }
-  void launch_rollout_policy(int32_t steps, const float *actions, const StepIO &io0, float *actions_out, hipStream_t s) {
-    // lane-asynchronous form (ArmEnvConfig.rollout_ready_lanes > 0): external actions or the in-kernel random policy
-    const bool fused_actor = !actions && (pol.kind == ARMENV_POLICY_ACTOR || pol.kind == ARMENV_POLICY_ACTOR_F16X3 || pol.kind == ARMENV_POLICY_DATD3 ||
-                                         pol.kind == ARMENV_POLICY_DADDPG);
-    if (ready_lanes > 0 && steps > 1 && !fused_actor) {
-      if (fence_on) {
-        with_book_lane([&](auto *tag) {
-          using LX = std::remove_pointer_t<decltype(tag)>;
-          if (actions) launch_rollout_async<ARMENV_POLICY_EXTERNAL, LX>(steps, actions, io0, actions_out, s);
-          else launch_rollout_async<ARMENV_POLICY_RANDOM, LX>(steps, actions, io0, actions_out, s);
-        });
-      } else {
-        if (actions) launch_rollout_async<ARMENV_POLICY_EXTERNAL>(steps, actions, io0, actions_out, s);
-        else launch_rollout_async<ARMENV_POLICY_RANDOM>(steps, actions, io0, actions_out, s);
+  template <int POLICY>
+  void launch_rollout(Family f, int32_t steps, const float *actions, const StepIO &io0, float *actions_out, hipStream_t s) {
+    constexpr bool kFused = fused_policy(POLICY);
+    const Launch G = geometry(f);
+    with_build<kFused>(G.two, [&](auto *lane, auto waves) {
+      using LX = std::remove_pointer_t<decltype(lane)>;
+      constexpr int W = decltype(waves)::value;
+      if constexpr (!kFused) {
+        if (f == Family::RolloutAsync) {
+          // count rule under half-filled waves: the same share of the live lanes (62 of 64 -> 31 of 32; 22.1 us vs 23.2 at 30)
+          const int32_t ready = G.P.half_waves ? (ready_lanes + 1) / 2 : ready_lanes;
+          hipLaunchKernelGGL((env_rollout_async_kernel<LX, T, POLICY, W>), G.grid, G.block, 0, s, G.P, pol, steps, actions, io0,
+                             actions_out, ready, (int32_t)straggler_trips);
+          return;
+        }
       }
-      return;
-    }
-    if (fence_on && !fused_actor) {   // the bookkeeping builds exist for external actions and the in-kernel random policy
-      with_book_lane([&](auto *tag) {
-        using LX = std::remove_pointer_t<decltype(tag)>;
-        if (actions) launch_rollout<ARMENV_POLICY_EXTERNAL, LX>(steps, actions, io0, actions_out, s);
-        else launch_rollout<ARMENV_POLICY_RANDOM, LX>(steps, actions, io0, actions_out, s);
-      });
-      return;
-    }
-    if (actions) launch_rollout<ARMENV_POLICY_EXTERNAL>(steps, actions, io0, actions_out, s);
-    else if (pol.kind == ARMENV_POLICY_ACTOR) launch_rollout<ARMENV_POLICY_ACTOR>(steps, actions, io0, actions_out, s);
-    else if (pol.kind == ARMENV_POLICY_ACTOR_F16X3) launch_rollout<ARMENV_POLICY_ACTOR_F16X3>(steps, actions, io0, actions_out, s);
-    else if (pol.kind == ARMENV_POLICY_DATD3 || pol.kind == ARMENV_POLICY_DADDPG)   // DADDPG: the same kernel over a net table whose two critics are one
-      launch_rollout<ARMENV_POLICY_DATD3>(steps, actions, io0, actions_out, s);
-    else launch_rollout<ARMENV_POLICY_RANDOM>(steps, actions, io0, actions_out, s);
+      hipLaunchKernelGGL((env_rollout_kernel<LX, T, POLICY, W>), G.grid, G.block, 0, s, G.P, pol, steps, actions, io0, actions_out);
+    });
   }
   int rollout(int32_t steps, const float *actions, const StepIO &io0, float *actions_out, hipStream_t s) override {
-    launch_rollout_policy(steps, actions, io0, actions_out, s);
+    // external actions and the in-kernel random policy: lane-asynchronous when ArmEnvConfig.rollout_ready_lanes > 0
+    const Family f = ready_lanes > 0 && steps > 1 ? Family::RolloutAsync : Family::Rollout;
+    if (actions) launch_rollout<ARMENV_POLICY_EXTERNAL>(f, steps, actions, io0, actions_out, s);
+    else if (pol.kind == ARMENV_POLICY_ACTOR) launch_rollout<ARMENV_POLICY_ACTOR>(Family::RolloutWg, steps, actions, io0, actions_out, s);
+    else if (pol.kind == ARMENV_POLICY_ACTOR_F16X3) launch_rollout<ARMENV_POLICY_ACTOR_F16X3>(Family::RolloutWg, steps, actions, io0, actions_out, s);
+    else if (fused_policy(pol.kind)) launch_rollout<ARMENV_POLICY_DATD3>(Family::RolloutWg, steps, actions, io0, actions_out, s);   // DATD3, DADDPG
+    else launch_rollout<ARMENV_POLICY_RANDOM>(f, steps, actions, io0, actions_out, s);
     HIP_TRY(hipGetLastError());
     return ARMENV_OK;
   }
