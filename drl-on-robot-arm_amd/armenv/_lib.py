@@ -4,7 +4,7 @@ import ctypes as C
 import os
 
 NJ = 7
-ABI_VERSION = 6
+ABI_VERSION = 7
 TASK_REACH, TASK_PUSH, TASK_PICK = 0, 1, 2
 ROBOT_KUKA, ROBOT_DIANA = 0, 1
 FK_AUTO, FK_GENERIC = 0, 1
@@ -67,6 +67,24 @@ class ArmEnvHerArgs(C.Structure):
     ]
 
 
+class ArmEnvMlpRW(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("W1", "b1", "W2", "b2", "W3", "b3")]
+
+
+class ArmEnvTd3Args(C.Structure):
+    _fields_ = (
+        [("device", C.c_int32), ("state_dim", C.c_int32), ("action_dim", C.c_int32), ("hidden_dim", C.c_int32), ("batch", C.c_int64)]
+        + [(k, C.c_float) for k in ("action_bound", "gamma", "tau", "policy_noise", "noise_clip", "actor_lr", "critic_lr",
+                                    "beta1", "beta2", "eps")]
+        + [("critic_step", C.c_int64), ("actor_step", C.c_int64), ("with_actor", C.c_int32), ("seed", C.c_uint64), ("draw", C.c_uint64),
+           ("noise_dev", C.c_void_p)]
+        + [(k, ArmEnvMlpRW) for k in ("actor", "q1", "q2", "target_actor", "target_q1", "target_q2",
+                                      "actor_m", "actor_v", "q1_m", "q1_v", "q2_m", "q2_v")]
+        + [(k, C.c_void_p) for k in ("states_dev", "actions_dev", "next_states_dev", "rewards_dev", "dones_dev", "loss_dev",
+                                     "workspace_dev")]
+        + [("workspace_bytes", C.c_int64)])
+
+
 # every symbol include/armenv.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -96,6 +114,8 @@ SYMBOLS = {
     "armenv_count_episodes": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P]),
     "armenv_write_episodes": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, _P, _P]),
     "armenv_her_sample": (C.c_int, [C.c_int32, C.POINTER(ArmEnvHerArgs), _P]),
+    "armenv_td3_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
+    "armenv_td3_update": (C.c_int, [C.POINTER(ArmEnvTd3Args), _P]),
     "armenv_probe_issue_rate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "armenv_probe_clock": (C.c_int, [C.c_int32, _P, C.POINTER(C.c_int32), _P]),
     "armenv_num_envs": (C.c_int64, [_P]),

@@ -7,6 +7,7 @@ instantiates (config.py:33, main.py:93): two actors and one critic, take_action 
 
     python -m armenv.train --iterations 200
     python -m armenv.train --iterations 200 --algo daddpg
+    python -m armenv.train --iterations 200 --learner hip      # the fused HIP TD3 update (armenv.fused_td3)
 """
 import argparse
 import json
@@ -17,22 +18,41 @@ import torch
 from . import envs
 from .replay import TrajectoryStore
 from .daddpg import DADDPG
+from .fused_td3 import FusedTD3
 from .td3 import TD3
+
+
+def _check_learner(algo, learner):
+    if learner not in ("torch", "hip"):
+        raise ValueError("learner must be 'torch' or 'hip'")
+    if learner == "hip" and algo != "td3":
+        raise ValueError("learner='hip' is the fused TD3 update: it needs algo='td3'")
+
+
+def _make_agent(algo, learner, state_dim, action_bound, device, batch_size, use_graphs, seed):
+    """(agent, static input buffers or None, whether the updates are replayed from hipGraphs)"""
+    if learner == "hip":
+        agent = FusedTD3(state_dim, 3, action_bound, device=device, seed=seed)
+        return agent, agent.batch_buffers(batch_size), False
+    agent = (DADDPG if algo == "daddpg" else TD3)(state_dim, 3, action_bound, device=device)   # getattr(algo, opt.algo)(...)
+    static = agent.capture(batch_size) if use_graphs else None     # TD3 update as hipGraphs: launch-bound otherwise
+    return agent, static, use_graphs
 
 
 def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, batch_size=2048, her_ratio=0.8, seed=0,
                 device="cuda:0", actor_kind="actor_f16x3", expl_sigma=0.7 * 0.98, log_every=10, log=print,
-                window_steps=1536, minimal_episodes=5, max_steps=500, use_graphs=True, algo="td3"):
+                window_steps=1536, minimal_episodes=5, max_steps=500, use_graphs=True, algo="td3", learner="torch"):
+    # learner="hip": the TD3 update is libarmenv's fused one (armenv.fused_td3.FusedTD3), issued directly: no capture, no graph.
     # use_graphs: the agent's update replayed from hipGraphs (GraphedLearner.capture): the update is ~130 small kernels, launch-bound
     # when issued one by one (160 iterations: 7 s against 14 s).  Round 6 found the replayed updates no longer learning and why: a
     # hipMemsetAsync captured into a hipGraph works on the first replay only on this ROCm build, torch's multi-block reductions
     # initialise their semaphores with one, so every captured bias gradient went wrong from the second replay on.  The captured update
     # now contains no such reduction (armenv.td3._CaptureSafeLinear; profiles/r06_td3_hipgraph_learning.txt) and learns like the eager one.
+    _check_learner(algo, learner)
     torch.manual_seed(seed)
     action_bound = 0.7                                            # main.py:87
     env = envs.BatchedReachEnv(num_envs, device=device, seed=seed, max_steps=max_steps)
-    agent = (DADDPG if algo == "daddpg" else TD3)(6, 3, action_bound, device=device)      # getattr(algo, opt.algo)(...), main.py:93
-    static = agent.capture(batch_size) if use_graphs else None     # TD3 update as hipGraphs: launch-bound otherwise
+    agent, static, use_graphs = _make_agent(algo, learner, 6, action_bound, device, batch_size, use_graphs, seed)  # main.py:93
     store = TrajectoryStore(device=device, seed=seed, capacity_steps=window_steps)   # last `window_steps` steps of every env
     ready = False
     obs = env.reset()
@@ -58,6 +78,8 @@ def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, bat
             for _ in range(updates):                              # main.py:136-138
                 if use_graphs:     # HER batch written straight into the captured update's static buffers
                     agent.train_graphed(store.sample(batch_size, use_her=True, her_ratio=her_ratio, out=static))
+                elif static is not None:     # fused learner: HER batch written into its static input buffers
+                    agent.train(store.sample(batch_size, use_her=True, her_ratio=her_ratio, out=static))
                 else:
                     agent.train(store.sample(batch_size, use_her=True, her_ratio=her_ratio))
         if (it + 1) % log_every == 0:
@@ -75,17 +97,17 @@ def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, bat
 
 def train_push(num_envs=1024, iterations=300, rollout_steps=32, updates=48, batch_size=2048, her_ratio=0.8, seed=0,
                device="cuda:0", actor_kind="actor_f16x3", log_every=10, log=print, window_steps=1536, minimal_episodes=5,
-               max_steps=500, task="push", use_graphs=True, algo="td3"):
+               max_steps=500, task="push", use_graphs=True, algo="td3", learner="torch"):
     """``train_push_with_TD3`` (/root/reference/main.py:449-515) on the device: state_dim 9, action_bound 0.4 (:455-457),
     unclipped exploration noise N(0, 0.4 * 0.98) (:484), push HER relabel rule (utils/rl_utils.py:171-188).  The cube
     follows the build's simplified push-out model, so learning curves are not comparable with the reference's.
     ``task="pick"`` is ``train_pick_with_TD3`` (main.py:518-585), the same loop around RLPickEnv."""
+    _check_learner(algo, learner)
     torch.manual_seed(seed)
     action_bound = 0.4
     Env = envs.BatchedPushEnv if task == "push" else envs.BatchedPickEnv
     env = Env(num_envs, device=device, seed=seed, max_steps=max_steps)
-    agent = (DADDPG if algo == "daddpg" else TD3)(9, 3, action_bound, device=device)
-    static = agent.capture(batch_size) if use_graphs else None
+    agent, static, use_graphs = _make_agent(algo, learner, 9, action_bound, device, batch_size, use_graphs, seed)
     store = TrajectoryStore(device=device, seed=seed, capacity_steps=window_steps)
     obs = env.reset()
     history, ready, bufs = [], False, {}
@@ -106,6 +128,8 @@ def train_push(num_envs=1024, iterations=300, rollout_steps=32, updates=48, batc
             for _ in range(updates):
                 if use_graphs:     # HER batch written straight into the captured update's static buffers
                     agent.train_graphed(store.sample(batch_size, use_her=True, her_ratio=her_ratio, out=static))
+                elif static is not None:     # fused learner: HER batch written into its static input buffers
+                    agent.train(store.sample(batch_size, use_her=True, her_ratio=her_ratio, out=static))
                 else:
                     agent.train(store.sample(batch_size, use_her=True, her_ratio=her_ratio))
         if (it + 1) % log_every == 0:
@@ -135,14 +159,17 @@ def main():
     ap.add_argument("--max-steps", type=int, default=500, help="opt.max_steps_one_episode")
     ap.add_argument("--graphs", type=int, default=1, help="1: the agent's updates replayed from hipGraphs (default); 0: issued eagerly")
     ap.add_argument("--algo", default="td3", choices=["td3", "daddpg"], help="the agent (config.py:33's default is DADDPG_MLP)")
+    ap.add_argument("--learner", default="torch", choices=["torch", "hip"],
+                    help="torch: the agent's update in torch (default); hip: libarmenv's fused TD3 update (--algo td3 only)")
     a = ap.parse_args()
     if a.task != "reach":
         train_push(a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed, actor_kind=a.actor,
-                   window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, use_graphs=a.graphs == 1, algo=a.algo)
+                   window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, use_graphs=a.graphs == 1, algo=a.algo,
+                   learner=a.learner)
         return
     train_reach(a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed, actor_kind=a.actor,
                 expl_sigma=a.sigma, window_steps=a.window_steps, max_steps=a.max_steps, algo=a.algo,
-                use_graphs=a.graphs == 1)
+                use_graphs=a.graphs == 1, learner=a.learner)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,380 @@
+// armenv_learner.h -- kernels of the fused TD3 update (armenv_td3_update, armenv_learner.hip): TD3_MLP.train
+// (the reference's algo/TD3/TD3_mlp.py:114-161) over the networks of net_mlp.py:29-71, hidden width 256, exact f32.
+//
+// Three kinds of kernel, each launched over a LIST of independent problems so that every stage of the update is one launch:
+//   gemm_kernel        C = A . B on v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: no xf32 on gfx950).  A 64 x 64 output tile
+//                      per 256-thread workgroup, 32 x 32 per wave, K streamed through LDS in slices of 16.  Every contraction
+//                      of the update is one of three forms of the same product, expressed through `Feat` operands:
+//                        forward       Y[b][o]  = X[b][:] . W[o][:]     (+ bias, relu)
+//                        backward      D1[b][i] = D2[b][:] . W[:][i]    (* relu'(H1))
+//                        weight grad   G[o][i]  = D[:][o] . X[:][i]     (K = the batch; [X | 1] gives the bias column)
+//                      Weight gradients are reduced over the batch in slices of LRN_KSPLIT rows: slice s writes its own partial
+//                      (no atomics); the optimiser kernel adds the partials in slice order.  Every sum of the update therefore has
+//                      one fixed order, and an update is bitwise reproducible run to run.
+//   *_head_kernel      the per-row work of the 256 -> 3 / 256 -> 1 layers: one wave per batch row, a 256-long dot product as
+//                      four values per lane and a fixed xor-butterfly, then the row's deltas.
+//   adam_kernel        torch.optim.Adam (no weight decay, bias correction from the step number) over all tensors of one optimiser,
+//                      the Polyak soft update of the matching target network folded in, and (critic) the loss.
+// No kernel uses atomics, scratch or a memset; nothing is allocated: all intermediates live in the caller's workspace.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "armenv_math.h"
+
+namespace armenv {
+namespace learner {
+
+constexpr int LRN_H = 256;        // hidden width (config.py:56)
+constexpr int LRN_A = 3;          // action dim
+constexpr int LRN_TM = 64, LRN_TN = 64, LRN_TK = 16;   // gemm_kernel's workgroup tile and K slice
+constexpr int LRN_KSPLIT = 256;   // batch rows per weight-gradient partial
+constexpr int LRN_MAX_GEMMS = 6;
+constexpr int LRN_MAX_TENSORS = 12;
+
+// A row-major "feature matrix" F[r][f]: features f < split come from p0 (row stride ld0), split <= f < nf from p1 (row stride ld1),
+// f == nf is a column of ones when `aug` (the bias column of a weight gradient), anything else reads 0.  Two pointers let cat(s, a)
+// feed the critics without being materialised.
+struct Feat {
+  const float *p0, *p1;
+  int ld0, ld1, split, nf, aug;
+  int64_t rows;
+};
+
+AE_DEV float feat_at(const Feat &F, int64_t r, int f) {
+  if (r >= F.rows) return 0.f;
+  if (f < F.split) return F.p0[r * F.ld0 + f];
+  if (f < F.nf) return F.p1[r * F.ld1 + (f - F.split)];
+  return (F.aug && f == F.nf) ? 1.f : 0.f;
+}
+
+enum { EPI_STORE = 0,        // C = acc
+       EPI_BIAS_RELU = 1,    // C = relu(acc + bias[n])
+       EPI_MASK = 2,         // C = acc * (mask[m][n] > 0)             (backward through a relu)
+       EPI_DRELU_W = 3 };    // C = (acc + bias[n] > 0) ? scale * w[n] : 0  (a 256 -> 1 layer's delta through the relu in front of it)
+
+// C[m][n] = sum_k A(m, k) B(k, n) with A(m, k) = ta ? a[k][m] : a[m][k] and B(k, n) = tb ? b[n][k] : b[k][n] (Feat indexing).
+// K is cut into `splits` ranges of kchunk; range s writes C + s * split_stride.
+struct Gemm {
+  Feat a, b;
+  int ta, tb;
+  int M, N;
+  int64_t K, kchunk;
+  int splits, tiles_m, tiles_n, first_block;
+  float *C;
+  int ldc;
+  int64_t split_stride;
+  int epi;
+  const float *bias, *mask, *w;
+  int ldm;
+  float scale;
+};
+
+struct GemmList {
+  Gemm g[LRN_MAX_GEMMS];
+  int n;
+};
+
+__global__ __launch_bounds__(256) void gemm_kernel(GemmList L) {
+  __shared__ float As[LRN_TK][LRN_TM + 4];
+  __shared__ float Bs[LRN_TK][LRN_TN + 4];
+  int pi = 0;
+  while (pi + 1 < L.n && (int)blockIdx.x >= L.g[pi + 1].first_block) ++pi;
+  const Gemm &G = L.g[pi];
+  int t = (int)blockIdx.x - G.first_block;
+  const int tn = t % G.tiles_n;
+  t /= G.tiles_n;
+  const int tm = t % G.tiles_m;
+  const int s = t / G.tiles_m;
+  const int m0 = tm * LRN_TM, n0 = tn * LRN_TN;
+  const int64_t kbeg = (int64_t)s * G.kchunk;
+  const int64_t kend = kbeg + G.kchunk < G.K ? kbeg + G.kchunk : G.K;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  typedef float f32x16 __attribute__((ext_vector_type(16)));
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+  for (int64_t k0 = kbeg; k0 < kend; k0 += LRN_TK) {
+    // stage the A and B slices; consecutive threads walk the operand's contiguous (feature) index
+#pragma unroll
+    for (int i = 0; i < LRN_TM * LRN_TK / 256; ++i) {
+      const int e = tid + 256 * i;
+      int mm, kk;
+      if (G.ta) { mm = e % LRN_TM; kk = e / LRN_TM; } else { kk = e % LRN_TK; mm = e / LRN_TK; }
+      const int64_t k = k0 + kk;
+      float v = 0.f;
+      if (k < kend) v = G.ta ? feat_at(G.a, k, m0 + mm) : feat_at(G.a, m0 + mm, (int)k);
+      As[kk][mm] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < LRN_TN * LRN_TK / 256; ++i) {
+      const int e = tid + 256 * i;
+      int nn, kk;
+      if (G.tb) { kk = e % LRN_TK; nn = e / LRN_TK; } else { nn = e % LRN_TN; kk = e / LRN_TN; }
+      const int64_t k = k0 + kk;
+      float v = 0.f;
+      if (k < kend) v = G.tb ? feat_at(G.b, n0 + nn, (int)k) : feat_at(G.b, k, n0 + nn);
+      Bs[kk][nn] = v;
+    }
+    __syncthreads();
+    // 32x32x2: lane l supplies A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]
+#pragma unroll
+    for (int kk = 0; kk < LRN_TK; kk += 2) {
+      const float av = As[kk + (lane >> 5)][wm + (lane & 31)];
+      const float bv = Bs[kk + (lane >> 5)][wn + (lane & 31)];
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  // accumulator r of lane l: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31
+  float *C = G.C + (int64_t)s * G.split_stride;
+  const int n = n0 + wn + (lane & 31);
+  if (n >= G.N) return;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int m = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (m >= G.M) continue;
+    float v = acc[r];
+    if (G.epi == EPI_BIAS_RELU) {
+      v = v + G.bias[n];
+      v = v > 0.f ? v : 0.f;
+    } else if (G.epi == EPI_MASK) {
+      v = G.mask[(int64_t)m * G.ldm + n] > 0.f ? v : 0.f;
+    } else if (G.epi == EPI_DRELU_W) {
+      v = (v + G.bias[n] > 0.f) ? G.scale * G.w[n] : 0.f;
+    }
+    C[(int64_t)m * G.ldc + n] = v;
+  }
+}
+
+AE_DEV float wave_sum(float x) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+
+// four hidden units per lane: h[b][4 lane .. 4 lane + 3]
+AE_DEV float4 row4(const float *p, int64_t b, int lane) { return reinterpret_cast<const float4 *>(p + b * LRN_H)[lane]; }
+AE_DEV float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
+// standard normal pair from two 32-bit words (Box-Muller in f32; u1 in (0, 1])
+AE_DEV void box_muller(uint32_t w0, uint32_t w1, float &z0, float &z1) {
+  const float u1 = (float)((w0 >> 8) + 1u) * (1.0f / 16777216.0f);
+  const float u2 = (float)(w1 >> 8) * (1.0f / 16777216.0f);
+  const float r = sqrtf(-2.0f * logf(u1));
+  float sn, cs;
+  sincosf(6.283185307179586f * u2, &sn, &cs);
+  z0 = r * cs;
+  z1 = r * sn;
+}
+
+struct ActorHeadArgs {
+  int64_t B;
+  // target rows: a2 = clamp(bound tanh(h2 W3^T + b3) + clamp(noise policy_noise, +-noise_clip), +-bound)
+  const float *t_h2, *t_W3, *t_b3, *noise;
+  uint64_t seed, draw;
+  float bound, policy_noise, noise_clip;
+  float *a2;
+  // actor rows (when `with_actor`): a = bound tanh(h2 W3^T + b3), and tanh kept for the backward pass
+  int with_actor;
+  const float *h2, *W3, *b3;
+  float *a, *tanh_out;
+};
+
+// blocks [0, ceil(B / 4)): target rows; the next ceil(B / 4): actor rows
+__global__ __launch_bounds__(256) void actor_head_kernel(ActorHeadArgs P) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nb = (P.B + 3) / 4;
+  const bool actor = (int64_t)blockIdx.x >= nb;
+  const int64_t b = ((int64_t)blockIdx.x - (actor ? nb : 0)) * 4 + (threadIdx.x >> 6);
+  if (b >= P.B) return;
+  const float *h2 = actor ? P.h2 : P.t_h2, *W3 = actor ? P.W3 : P.t_W3, *b3 = actor ? P.b3 : P.t_b3;
+  const float4 h = row4(h2, b, lane);
+  float u[LRN_A];
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) u[j] = wave_sum(dot4(h, row4(W3, j, lane))) + b3[j];
+  if (lane != 0) return;
+  if (actor) {
+#pragma unroll
+    for (int j = 0; j < LRN_A; ++j) {
+      const float th = tanhf(u[j]);
+      P.tanh_out[b * LRN_A + j] = th;
+      P.a[b * LRN_A + j] = th * P.bound;
+    }
+    return;
+  }
+  float z[4];
+  if (P.noise) {
+#pragma unroll
+    for (int j = 0; j < LRN_A; ++j) z[j] = P.noise[b * LRN_A + j];
+  } else {
+    // Philox4x32-10 keyed by seed, counter (row, draw): independent of launch geometry
+    uint32_t c[4] = {(uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)P.draw, (uint32_t)(P.draw >> 32)};
+    philox4x32_10(c, (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
+    box_muller(c[0], c[1], z[0], z[1]);
+    box_muller(c[2], c[3], z[2], z[3]);
+  }
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) {
+    const float nz = fminf(fmaxf(z[j] * P.policy_noise, -P.noise_clip), P.noise_clip);
+    const float v = tanhf(u[j]) * P.bound + nz;
+    P.a2[b * LRN_A + j] = fminf(fmaxf(v, -P.bound), P.bound);
+  }
+}
+
+struct CriticHeadArgs {
+  int64_t B;
+  float gamma, inv_b;
+  const float *rewards;
+  const uint8_t *dones;
+  const float *t_h2[2], *t_W3[2], *t_b3[2];    // target twin critic's last hidden layer and fc3 / fc6
+  const float *h2[2], *W3[2], *b3[2];          // critic's
+  float *d3[2];                                // out [B]: dLoss / dq
+  float *d2[2];                                // out [B][H]: (d3 W3) * relu'(h2)
+  float *loss_rows;                            // out [B][2]: (q1 - target)^2, (q2 - target)^2
+};
+
+// target = r + (1 - d) gamma min(tq1, tq2); loss = mse(q1, target) + mse(q2, target) and its deltas, one wave per row
+__global__ __launch_bounds__(256) void critic_head_kernel(CriticHeadArgs P) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= P.B) return;
+  float tq[2], q[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    tq[i] = wave_sum(dot4(row4(P.t_h2[i], b, lane), row4(P.t_W3[i], 0, lane))) + P.t_b3[i][0];
+    q[i] = wave_sum(dot4(row4(P.h2[i], b, lane), row4(P.W3[i], 0, lane))) + P.b3[i][0];
+  }
+  const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
+  const float target = P.rewards[b] + notdone * P.gamma * fminf(tq[0], tq[1]);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const float e = q[i] - target;
+    const float d3 = 2.0f * e * P.inv_b;
+    if (lane == 0) {
+      P.d3[i][b] = d3;
+      P.loss_rows[2 * b + i] = e * e;
+    }
+    const float4 h = row4(P.h2[i], b, lane), w = row4(P.W3[i], 0, lane);
+    float4 d;
+    d.x = h.x > 0.f ? d3 * w.x : 0.f;
+    d.y = h.y > 0.f ? d3 * w.y : 0.f;
+    d.z = h.z > 0.f ? d3 * w.z : 0.f;
+    d.w = h.w > 0.f ? d3 * w.w : 0.f;
+    reinterpret_cast<float4 *>(P.d2[i] + b * LRN_H)[lane] = d;
+  }
+}
+
+struct ActorBackArgs {
+  int64_t B;
+  int in_dim;            // state_dim + 3: row length of Q1's fc1 weight
+  int state_dim;
+  float bound;
+  const float *dc1;      // [B][H]: delta at Q1's first hidden layer
+  const float *Wq1;      // [H][in_dim]
+  const float *tanh_a;   // [B][3]
+  const float *h2, *W3;  // actor's last hidden layer [B][H], fc3 weight [3][H]
+  float *du;             // out [B][3]: delta at the actor's pre-tanh output
+  float *da2;            // out [B][H]: (du W3) * relu'(h2)
+};
+
+// back through cat(s, a) -> a = bound tanh(u) -> fc3 of the actor, one wave per row
+__global__ __launch_bounds__(256) void actor_back_kernel(ActorBackArgs P) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= P.B) return;
+  const float4 d = row4(P.dc1, b, lane);
+  float du[LRN_A];
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) {
+    const float *w = P.Wq1 + P.state_dim + j;
+    float4 wc;
+    wc.x = w[(4 * lane + 0) * P.in_dim];
+    wc.y = w[(4 * lane + 1) * P.in_dim];
+    wc.z = w[(4 * lane + 2) * P.in_dim];
+    wc.w = w[(4 * lane + 3) * P.in_dim];
+    const float da = wave_sum(dot4(d, wc));
+    const float th = P.tanh_a[b * LRN_A + j];
+    du[j] = da * P.bound * (1.0f - th * th);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < LRN_A; ++j) P.du[b * LRN_A + j] = du[j];
+  }
+  const float4 h = row4(P.h2, b, lane);
+  float4 w0 = row4(P.W3, 0, lane), w1 = row4(P.W3, 1, lane), w2 = row4(P.W3, 2, lane), o;
+  o.x = h.x > 0.f ? du[0] * w0.x + du[1] * w1.x + du[2] * w2.x : 0.f;
+  o.y = h.y > 0.f ? du[0] * w0.y + du[1] * w1.y + du[2] * w2.y : 0.f;
+  o.z = h.z > 0.f ? du[0] * w0.z + du[1] * w1.z + du[2] * w2.z : 0.f;
+  o.w = h.w > 0.f ? du[0] * w0.w + du[1] * w1.w + du[2] * w2.w : 0.f;
+  reinterpret_cast<float4 *>(P.da2 + b * LRN_H)[lane] = o;
+}
+
+// One parameter tensor of an optimiser: `rows` x `cols` elements; its gradient is sum_s partial[s * split_stride + r * ldp + c0 + c].
+struct AdamTensor {
+  float *p, *m, *v, *tp;     // tp: the target network's tensor (soft-updated when AdamArgs.soft)
+  const float *partial;
+  int rows, cols, ldp, c0;
+  int first;                 // index of the tensor's first element in the launch
+};
+
+struct AdamArgs {
+  AdamTensor t[LRN_MAX_TENSORS];
+  int n, total, splits;
+  int64_t split_stride;
+  float step_size, bc2_sqrt, beta1, beta2, eps, tau;
+  int soft;
+  // the critic's launch also reduces the loss: one extra block after the elementwise ones
+  const float *loss_rows;
+  int64_t B;
+  float inv_b;
+  float *loss;
+};
+
+__global__ __launch_bounds__(256) void adam_kernel(AdamArgs P) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t elem_blocks = ((int64_t)P.total + 255) / 256;
+  if ((int64_t)blockIdx.x >= elem_blocks) {
+    // loss = mean((q1 - t)^2) + mean((q2 - t)^2), summed in a fixed order
+    __shared__ float red[2][256];
+    float s0 = 0.f, s1 = 0.f;
+    for (int64_t b = threadIdx.x; b < P.B; b += 256) {
+      s0 += P.loss_rows[2 * b];
+      s1 += P.loss_rows[2 * b + 1];
+    }
+    red[0][threadIdx.x] = s0;
+    red[1][threadIdx.x] = s1;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+      if ((int)threadIdx.x < o) {
+        red[0][threadIdx.x] += red[0][threadIdx.x + o];
+        red[1][threadIdx.x] += red[1][threadIdx.x + o];
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0 && P.loss) P.loss[0] = red[0][0] * P.inv_b + red[1][0] * P.inv_b;
+    return;
+  }
+  if (e >= P.total) return;
+  int ti = 0;
+  while (ti + 1 < P.n && e >= P.t[ti + 1].first) ++ti;
+  const AdamTensor &T = P.t[ti];
+  const int i = (int)(e - T.first);
+  const int r = i / T.cols, c = i % T.cols;
+  const float *g_p = T.partial + (int64_t)r * T.ldp + T.c0 + c;
+  float g = 0.f;
+  for (int s = 0; s < P.splits; ++s) g += g_p[(int64_t)s * P.split_stride];
+  const float m = P.beta1 * T.m[i] + (1.0f - P.beta1) * g;
+  const float v = P.beta2 * T.v[i] + (1.0f - P.beta2) * g * g;
+  T.m[i] = m;
+  T.v[i] = v;
+  const float p = T.p[i] - P.step_size * m / (sqrtf(v) / P.bc2_sqrt + P.eps);
+  T.p[i] = p;
+  if (P.soft) T.tp[i] = T.tp[i] * (1.0f - P.tau) + P.tau * p;
+}
+
+}  // namespace learner
+}  // namespace armenv

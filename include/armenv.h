@@ -35,7 +35,8 @@ extern "C" {
 #endif
 
 #define ARMENV_NJ 7
-#define ARMENV_ABI_VERSION 6   /* 6: + armenv_set_policy_daddpg, armenv_episode_returns_f32, ARMENV_POLICY_DADDPG; ArmEnvConfig unchanged since 5 */
+#define ARMENV_ABI_VERSION 7   /* 7: + armenv_td3_update, armenv_td3_workspace_bytes, ArmEnvMlpRW, ArmEnvTd3Args;
+                                  6: + armenv_set_policy_daddpg, armenv_episode_returns_f32, ARMENV_POLICY_DADDPG; ArmEnvConfig unchanged since 5 */
 
 enum {
   ARMENV_OK = 0,
@@ -433,6 +434,47 @@ typedef struct ArmEnvHerArgs {
  * uniform episode, uniform step, with probability her_ratio a future state's first three dims become the goal,
  * reward -0.1 / 1.0 and done by the distance threshold. */
 int armenv_her_sample(int32_t device, const ArmEnvHerArgs *args, void *stream);
+
+/* ---- fused TD3 learner: one TD3_MLP.train update (the reference's algo/TD3/TD3_mlp.py:114-161) over the networks of
+ * net_mlp.py:29-71 (actor: fc1-3, tanh x action_bound; twin critic over cat(s, a): fc1-3 = Q1, fc4-6 = Q2), hidden_dim 256:
+ *   noise  = clamp(N(0,1) policy_noise, +-noise_clip);  a2 = clamp(target_actor(s2) + noise, +-action_bound)
+ *   target = r + (1 - d) gamma min(target_Q1(s2, a2), target_Q2(s2, a2))
+ *   critic: loss = mse(Q1(s, a), target) + mse(Q2(s, a), target), one Adam step
+ *   with_actor (the caller's total_it % policy_freq == 0): actor loss -mean(Q1(s, actor(s))) with the critic AFTER its step, one
+ *   Adam step on the actor, then Polyak soft updates (tau) of the target actor and the target critic.
+ * Adam is torch.optim.Adam's: no weight decay, bias corrections 1 - beta^step from the 1-based step numbers passed in.
+ * Parameters, targets and moments are updated in place.  The noise is Philox4x32-10 keyed by (seed, row, draw), Box-Muller in
+ * f32; noise_dev (nullable, [B][action_dim] standard normals) replaces it.
+ *
+ * Properties: every contraction runs on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32); batch sums are taken in a fixed order
+ * (per-slice partials added in slice order; no atomics), so an update is bitwise reproducible run to run.  The call only
+ * enqueues kernels on `stream`: 9 launches, 16 with the actor step; no allocation, no memset, no host synchronisation, so it
+ * can be captured into a graph.  All intermediates live in the caller's workspace (armenv_td3_workspace_bytes).
+ * Every argument is validated before any HIP call: a bad one returns ARMENV_EINVAL and armenv_last_error() names the field. */
+typedef struct ArmEnvMlpRW {
+  float *W1, *b1, *W2, *b2, *W3, *b3;      /* torch Linear layout, as ArmEnvMlp */
+} ArmEnvMlpRW;
+
+typedef struct ArmEnvTd3Args {
+  int32_t device, state_dim, action_dim, hidden_dim;   /* state_dim 1..12 (6 reach, 9 push / pick), action_dim 3, hidden_dim 256 */
+  int64_t batch;                                       /* B >= 1, any size */
+  float action_bound, gamma, tau, policy_noise, noise_clip, actor_lr, critic_lr, beta1, beta2, eps;
+  int64_t critic_step, actor_step;                     /* 1-based Adam step numbers of THIS update (actor_step read if with_actor) */
+  int32_t with_actor;                                  /* 0 or 1 */
+  uint64_t seed, draw;
+  const float *noise_dev;                              /* nullable [B][action_dim] standard normals */
+  ArmEnvMlpRW actor, q1, q2, target_actor, target_q1, target_q2;   /* q1 = critic fc1-3, q2 = fc4-6 */
+  ArmEnvMlpRW actor_m, actor_v, q1_m, q1_v, q2_m, q2_v;            /* Adam moments, same shapes */
+  const float *states_dev, *actions_dev, *next_states_dev, *rewards_dev;   /* [B][state_dim], [B][3], [B][state_dim], [B] */
+  const uint8_t *dones_dev;                            /* [B] */
+  float *loss_dev;                                     /* nullable out: f32 scalar critic loss */
+  void *workspace_dev;                                 /* device, 16-byte aligned */
+  int64_t workspace_bytes;
+} ArmEnvTd3Args;
+
+/* Bytes of workspace armenv_td3_update needs for (state_dim, hidden_dim, batch); -1 for unsupported sizes. */
+int64_t armenv_td3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch);
+int armenv_td3_update(const ArmEnvTd3Args *args, void *stream);
 
 /* Measurement aid (bench.py's roofline.valu.one_wave_per_simd; no reference counterpart): the interval at which SIMDs issue
  * independent 64-lane v_fma_f64 (precision 64) / v_fma_f32 (32) instructions when every SIMD of `device` holds
