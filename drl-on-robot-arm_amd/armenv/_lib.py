@@ -4,7 +4,7 @@ import ctypes as C
 import os
 
 NJ = 7
-ABI_VERSION = 7
+ABI_VERSION = 8
 TASK_REACH, TASK_PUSH, TASK_PICK = 0, 1, 2
 ROBOT_KUKA, ROBOT_DIANA = 0, 1
 FK_AUTO, FK_GENERIC = 0, 1
@@ -85,6 +85,18 @@ class ArmEnvTd3Args(C.Structure):
         + [("workspace_bytes", C.c_int64)])
 
 
+class ArmEnvDaddpgArgs(C.Structure):
+    _fields_ = (
+        [("device", C.c_int32), ("state_dim", C.c_int32), ("action_dim", C.c_int32), ("hidden_dim", C.c_int32), ("batch", C.c_int64)]
+        + [(k, C.c_float) for k in ("action_bound", "gamma", "tau", "actor_lr", "critic_lr", "beta1", "beta2", "eps")]
+        + [("critic_step", C.c_int64), ("actor_step", C.c_int64), ("update_actor", C.c_int32)]
+        + [(k, ArmEnvMlpRW) for k in ("actor1", "actor2", "critic", "target_actor1", "target_actor2", "target_critic",
+                                      "actor1_m", "actor1_v", "actor2_m", "actor2_v", "critic_m", "critic_v")]
+        + [(k, C.c_void_p) for k in ("states_dev", "actions_dev", "next_states_dev", "rewards_dev", "dones_dev", "loss_dev",
+                                     "workspace_dev")]
+        + [("workspace_bytes", C.c_int64)])
+
+
 # every symbol include/armenv.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -116,6 +128,8 @@ SYMBOLS = {
     "armenv_her_sample": (C.c_int, [C.c_int32, C.POINTER(ArmEnvHerArgs), _P]),
     "armenv_td3_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     "armenv_td3_update": (C.c_int, [C.POINTER(ArmEnvTd3Args), _P]),
+    "armenv_daddpg_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
+    "armenv_daddpg_update": (C.c_int, [C.POINTER(ArmEnvDaddpgArgs), _P]),
     "armenv_probe_issue_rate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "armenv_probe_clock": (C.c_int, [C.c_int32, _P, C.POINTER(C.c_int32), _P]),
     "armenv_num_envs": (C.c_int64, [_P]),

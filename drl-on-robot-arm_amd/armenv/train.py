@@ -8,6 +8,7 @@ instantiates (config.py:33, main.py:93): two actors and one critic, take_action 
     python -m armenv.train --iterations 200
     python -m armenv.train --iterations 200 --algo daddpg
     python -m armenv.train --iterations 200 --learner hip      # the fused HIP TD3 update (armenv.fused_td3)
+    python -m armenv.train --iterations 200 --algo daddpg --learner fused    # the agent's own fused HIP update (armenv.fused_daddpg)
 """
 import argparse
 import json
@@ -18,21 +19,25 @@ import torch
 from . import envs
 from .replay import TrajectoryStore
 from .daddpg import DADDPG
+from .fused_daddpg import FusedDADDPG
 from .fused_td3 import FusedTD3
 from .td3 import TD3
 
 
 def _check_learner(algo, learner):
-    if learner not in ("torch", "hip"):
-        raise ValueError("learner must be 'torch' or 'hip'")
+    if learner not in ("torch", "hip", "fused"):
+        raise ValueError("learner must be 'torch', 'hip' or 'fused'")
     if learner == "hip" and algo != "td3":
-        raise ValueError("learner='hip' is the fused TD3 update: it needs algo='td3'")
+        raise ValueError("learner='hip' is the fused TD3 update: it needs algo='td3' (learner='fused' is the agent's own fused update)")
 
 
 def _make_agent(algo, learner, state_dim, action_bound, device, batch_size, use_graphs, seed):
     """(agent, static input buffers or None, whether the updates are replayed from hipGraphs)"""
-    if learner == "hip":
-        agent = FusedTD3(state_dim, 3, action_bound, device=device, seed=seed)
+    if learner in ("hip", "fused"):       # "hip": FusedTD3 (td3 only); "fused": the agent's own fused update
+        if algo == "daddpg":
+            agent = FusedDADDPG(state_dim, 3, action_bound, device=device)
+        else:
+            agent = FusedTD3(state_dim, 3, action_bound, device=device, seed=seed)
         return agent, agent.batch_buffers(batch_size), False
     agent = (DADDPG if algo == "daddpg" else TD3)(state_dim, 3, action_bound, device=device)   # getattr(algo, opt.algo)(...)
     static = agent.capture(batch_size) if use_graphs else None     # TD3 update as hipGraphs: launch-bound otherwise
@@ -43,6 +48,7 @@ def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, bat
                 device="cuda:0", actor_kind="actor_f16x3", expl_sigma=0.7 * 0.98, log_every=10, log=print,
                 window_steps=1536, minimal_episodes=5, max_steps=500, use_graphs=True, algo="td3", learner="torch"):
     # learner="hip": the TD3 update is libarmenv's fused one (armenv.fused_td3.FusedTD3), issued directly: no capture, no graph.
+    # learner="fused": the agent's own fused update -- FusedTD3 for td3, armenv.fused_daddpg.FusedDADDPG for daddpg.
     # use_graphs: the agent's update replayed from hipGraphs (GraphedLearner.capture): the update is ~130 small kernels, launch-bound
     # when issued one by one (160 iterations: 7 s against 14 s).  Round 6 found the replayed updates no longer learning and why: a
     # hipMemsetAsync captured into a hipGraph works on the first replay only on this ROCm build, torch's multi-block reductions
@@ -159,8 +165,9 @@ def main():
     ap.add_argument("--max-steps", type=int, default=500, help="opt.max_steps_one_episode")
     ap.add_argument("--graphs", type=int, default=1, help="1: the agent's updates replayed from hipGraphs (default); 0: issued eagerly")
     ap.add_argument("--algo", default="td3", choices=["td3", "daddpg"], help="the agent (config.py:33's default is DADDPG_MLP)")
-    ap.add_argument("--learner", default="torch", choices=["torch", "hip"],
-                    help="torch: the agent's update in torch (default); hip: libarmenv's fused TD3 update (--algo td3 only)")
+    ap.add_argument("--learner", default="torch", choices=["torch", "hip", "fused"],
+                    help="torch: the agent's update in torch (default); hip: libarmenv's fused TD3 update (--algo td3 only); "
+                         "fused: the agent's own fused HIP update (FusedTD3 or FusedDADDPG)")
     a = ap.parse_args()
     if a.task != "reach":
         train_push(a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed, actor_kind=a.actor,

@@ -1,5 +1,6 @@
-// armenv_learner.h -- kernels of the fused TD3 update (armenv_td3_update, armenv_learner.hip): TD3_MLP.train
-// (the reference's algo/TD3/TD3_mlp.py:114-161) over the networks of net_mlp.py:29-71, hidden width 256, exact f32.
+// armenv_learner.h -- kernels of the fused learner updates (armenv_learner.hip): armenv_td3_update, TD3_MLP.train (the reference's
+// algo/TD3/TD3_mlp.py:114-161), and armenv_daddpg_update, DADDPG_MLP.update (algo/DADDPG/DADDPG_mlp.py:117-171), over the networks
+// of net_mlp.py, hidden width 256, exact f32.
 //
 // Three kinds of kernel, each launched over a LIST of independent problems so that every stage of the update is one launch:
 //   gemm_kernel        C = A . B on v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: no xf32 on gfx950).  A 64 x 64 output tile
@@ -15,6 +16,8 @@
 //                      four values per lane and a fixed xor-butterfly, then the row's deltas.
 //   adam_kernel        torch.optim.Adam (no weight decay, bias correction from the step number) over all tensors of one optimiser,
 //                      the Polyak soft update of the matching target network folded in, and (critic) the loss.
+// The DADDPG update shares gemm_kernel, actor_back_kernel and adam_kernel; its two per-row heads are daddpg_actor_head_kernel and
+// daddpg_critic_head_kernel (two actors and their targets, ONE critic, no target-policy noise).
 // No kernel uses atomics, scratch or a memset; nothing is allocated: all intermediates live in the caller's workspace.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -268,6 +271,74 @@ __global__ __launch_bounds__(256) void critic_head_kernel(CriticHeadArgs P) {
   }
 }
 
+struct DaddpgActorHeadArgs {
+  int64_t B;
+  float bound;
+  // problem k: a_k = bound tanh(h2_k W3_k^T + b3_k); k = 0, 1 the two target actors over s2, k = 2 the updated actor over s
+  const float *h2[3], *W3[3], *b3[3];
+  float *a[3];               // out [B][3] each
+  float *tanh_out;           // out [B][3]: tanh of problem 2, kept for the backward pass
+};
+
+// blocks [k ceil(B / 4), (k + 1) ceil(B / 4)): rows of problem k; no noise, no clamp (DADDPG_mlp.py:131-134)
+__global__ __launch_bounds__(256) void daddpg_actor_head_kernel(DaddpgActorHeadArgs P) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nb = (P.B + 3) / 4;
+  const int k = (int)((int64_t)blockIdx.x / nb);
+  const int64_t b = ((int64_t)blockIdx.x - k * nb) * 4 + (threadIdx.x >> 6);
+  if (k > 2 || b >= P.B) return;
+  const float4 h = row4(P.h2[k], b, lane);
+  float u[LRN_A];
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) u[j] = wave_sum(dot4(h, row4(P.W3[k], j, lane))) + P.b3[k][j];
+  if (lane != 0) return;
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) {
+    const float th = tanhf(u[j]);
+    if (k == 2) P.tanh_out[b * LRN_A + j] = th;
+    P.a[k][b * LRN_A + j] = th * P.bound;
+  }
+}
+
+struct DaddpgCriticHeadArgs {
+  int64_t B;
+  float gamma, inv_b;
+  const float *rewards;
+  const uint8_t *dones;
+  const float *t_h2[2];                        // the target critic's last hidden layer over cat(s2, a2_1) and cat(s2, a2_2)
+  const float *t_W3, *t_b3;                    // the target critic's fc3
+  const float *h2, *W3, *b3;                   // the critic's, over cat(s, a)
+  float *d3;                                   // out [B]: dLoss / dq
+  float *d2;                                   // out [B][H]: (d3 W3) * relu'(h2)
+  float *loss_rows;                            // out [B]: (q - target)^2
+};
+
+// target = r + (1 - d) gamma min(tq(a2_1), tq(a2_2)); loss = mse(q, target) and its deltas, one wave per row
+__global__ __launch_bounds__(256) void daddpg_critic_head_kernel(DaddpgCriticHeadArgs P) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= P.B) return;
+  const float4 tw = row4(P.t_W3, 0, lane);
+  const float tq0 = wave_sum(dot4(row4(P.t_h2[0], b, lane), tw)) + P.t_b3[0];
+  const float tq1 = wave_sum(dot4(row4(P.t_h2[1], b, lane), tw)) + P.t_b3[0];
+  const float4 h = row4(P.h2, b, lane), w = row4(P.W3, 0, lane);
+  const float q = wave_sum(dot4(h, w)) + P.b3[0];
+  const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
+  const float target = P.rewards[b] + notdone * P.gamma * fminf(tq0, tq1);
+  const float e = q - target;
+  const float d3 = 2.0f * e * P.inv_b;
+  if (lane == 0) {
+    P.d3[b] = d3;
+    P.loss_rows[b] = e * e;
+  }
+  float4 d;
+  d.x = h.x > 0.f ? d3 * w.x : 0.f;
+  d.y = h.y > 0.f ? d3 * w.y : 0.f;
+  d.z = h.z > 0.f ? d3 * w.z : 0.f;
+  d.w = h.w > 0.f ? d3 * w.w : 0.f;
+  reinterpret_cast<float4 *>(P.d2 + b * LRN_H)[lane] = d;
+}
+
 struct ActorBackArgs {
   int64_t B;
   int in_dim;            // state_dim + 3: row length of Q1's fc1 weight
@@ -329,6 +400,7 @@ struct AdamArgs {
   int soft;
   // the critic's launch also reduces the loss: one extra block after the elementwise ones
   const float *loss_rows;
+  int loss_cols;             // loss_rows is [B][loss_cols]: 2 (TD3's twin critic) or 1 (DADDPG's one critic)
   int64_t B;
   float inv_b;
   float *loss;
@@ -338,12 +410,16 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs P) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t elem_blocks = ((int64_t)P.total + 255) / 256;
   if ((int64_t)blockIdx.x >= elem_blocks) {
-    // loss = mean((q1 - t)^2) + mean((q2 - t)^2), summed in a fixed order
+    // loss = mean((q1 - t)^2) + mean((q2 - t)^2) (one column: mean((q - t)^2)), summed in a fixed order
     __shared__ float red[2][256];
     float s0 = 0.f, s1 = 0.f;
-    for (int64_t b = threadIdx.x; b < P.B; b += 256) {
-      s0 += P.loss_rows[2 * b];
-      s1 += P.loss_rows[2 * b + 1];
+    if (P.loss_cols == 2) {
+      for (int64_t b = threadIdx.x; b < P.B; b += 256) {
+        s0 += P.loss_rows[2 * b];
+        s1 += P.loss_rows[2 * b + 1];
+      }
+    } else {
+      for (int64_t b = threadIdx.x; b < P.B; b += 256) s0 += P.loss_rows[b];
     }
     red[0][threadIdx.x] = s0;
     red[1][threadIdx.x] = s1;
@@ -355,7 +431,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs P) {
       }
       __syncthreads();
     }
-    if (threadIdx.x == 0 && P.loss) P.loss[0] = red[0][0] * P.inv_b + red[1][0] * P.inv_b;
+    if (threadIdx.x == 0 && P.loss) P.loss[0] = P.loss_cols == 2 ? red[0][0] * P.inv_b + red[1][0] * P.inv_b : red[0][0] * P.inv_b;
     return;
   }
   if (e >= P.total) return;

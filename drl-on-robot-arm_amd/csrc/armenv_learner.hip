@@ -1,7 +1,8 @@
-// armenv_learner.hip -- armenv_td3_update / armenv_td3_workspace_bytes (include/armenv.h): argument checks, workspace layout and
-// the launch sequence of the fused TD3 update over the kernels of armenv_learner.h.
+// armenv_learner.hip -- armenv_td3_update / armenv_td3_workspace_bytes and armenv_daddpg_update / armenv_daddpg_workspace_bytes
+// (include/armenv.h): argument checks, workspace layouts and the launch sequences of the fused TD3 and DADDPG updates over the
+// kernels of armenv_learner.h.
 //
-// Launches (B rows, H = 256, D = state_dim, K1 = D + 3); every stage is one launch over all its independent problems:
+// TD3 launches (B rows, H = 256, D = state_dim, K1 = D + 3); every stage is one launch over all its independent problems:
 //   1 gemm    layer 1: target actor (s2), critic Q1 and Q2 (cat(s, a)), actor (s) when with_actor
 //   2 gemm    layer 2 of the same nets
 //   3 head    target actor's fc3 + noise -> a2; actor's fc3 -> a = actor(s) (the actor pass's forward needs no critic)
@@ -19,6 +20,18 @@
 //  14 gemm    da1 = (da2 W2a) relu'(h1a); dW3a | db3a and dW2a | db2a partials
 //  15 gemm    dW1a | db1a partials
 //  16 adam    actor (6 tensors) + the target actor's soft update
+//
+// DADDPG launches (two actors, ONE critic; actor k = update_actor is stepped), always 16:
+//   1 gemm    layer 1: target actors 1 and 2 (s2), critic (cat(s, a)), actor k (s)
+//   2 gemm    layer 2 of the same nets
+//   3 head    target actors' fc3 -> a2_1, a2_2 (no noise, no clamp); actor k's fc3 -> a = actor_k(s) and its tanh
+//   4 gemm    layer 1 of the target critic over cat(s2, a2_1) and cat(s2, a2_2)
+//   5 gemm    layer 2 of the same two problems
+//   6 head    target = r + (1 - d) gamma min(tq1, tq2), the critic's fc3, loss rows, d3 and d2 = (d3 W3) relu'(h2)
+//   7 gemm    d1 = (d2 W2) relu'(h1); dW3 | db3 and dW2 | db2 partials
+//   8 gemm    dW1 | db1 partials
+//   9 adam    critic (6 tensors) + the loss; update_actor == 2: the target critic's soft update (the critic is final by then)
+//  10-16      as TD3's 10-16 with the ONE critic in Q1's place and actor k in the actor's; 16 soft-updates target actor k only
 #include <cmath>
 
 #include "armenv_engine.h"
@@ -146,7 +159,9 @@ void adam_tensors(AdamArgs &P, const ArmEnvMlpRW &p, const ArmEnvMlpRW &m, const
   }
 }
 
-int launch_adam(AdamArgs &P, float lr, int64_t step, const ArmEnvTd3Args *a, hipStream_t s) {
+// Args: ArmEnvTd3Args or ArmEnvDaddpgArgs (beta1, beta2, eps, tau)
+template <class Args>
+int launch_adam(AdamArgs &P, float lr, int64_t step, const Args *a, hipStream_t s) {
   P.beta1 = a->beta1; P.beta2 = a->beta2; P.eps = a->eps; P.tau = a->tau;
   const double bc1 = 1.0 - std::pow((double)a->beta1, (double)step), bc2 = 1.0 - std::pow((double)a->beta2, (double)step);
   P.step_size = (float)(lr / bc1);
@@ -163,6 +178,78 @@ bool mlp_aligned(const ArmEnvMlpRW &m) { return al16(m.W1) && al16(m.b1) && al16
 
 constexpr int64_t kMaxBatch = (int64_t)1 << 20;
 
+// Argument checks both updates share (Args: ArmEnvTd3Args or ArmEnvDaddpgArgs); each names the field it refuses.
+template <class Args>
+int check_sizes(const char *fn, const Args *a) {
+  if (!a) return fail(ARMENV_EINVAL, "%s: args is NULL", fn);
+  if (a->device < 0) return fail(ARMENV_EINVAL, "%s: device %d", fn, a->device);
+  if (a->state_dim < 1 || a->state_dim > 12) return fail(ARMENV_EINVAL, "%s: state_dim %d outside 1..12", fn, a->state_dim);
+  if (a->action_dim != LRN_A) return fail(ARMENV_EINVAL, "%s: action_dim %d; the fused update is built for 3", fn, a->action_dim);
+  if (a->hidden_dim != LRN_H) return fail(ARMENV_EINVAL, "%s: hidden_dim %d; the fused update is built for %d", fn, a->hidden_dim, LRN_H);
+  if (a->batch < 1 || a->batch > kMaxBatch) return fail(ARMENV_EINVAL, "%s: batch %lld outside 1..%lld", fn, (long long)a->batch, (long long)kMaxBatch);
+  return ARMENV_OK;
+}
+
+struct NamedF { const char *name; float v; bool ok; };
+struct NamedNet { const char *name; const ArmEnvMlpRW *m; };
+
+// hyper-parameters, the nets and moments, the batch buffers and the workspace (`need` bytes)
+template <class Args, size_t NH, size_t NN>
+int check_buffers(const char *fn, const Args *a, const NamedF (&hp)[NH], const NamedNet (&nets)[NN], int64_t need, const char *ws_fn) {
+  for (const auto &h : hp)
+    if (!std::isfinite(h.v) || !h.ok) return fail(ARMENV_EINVAL, "%s: %s = %g out of range", fn, h.name, (double)h.v);
+  for (const auto &n : nets) {
+    if (!mlp_ok(*n.m)) return fail(ARMENV_EINVAL, "%s: %s has a NULL pointer", fn, n.name);
+    if (!mlp_aligned(*n.m)) return fail(ARMENV_EINVAL, "%s: %s has a pointer that is not 16-byte aligned", fn, n.name);
+  }
+  const struct { const char *name; const void *p; } bufs[] = {
+      {"states_dev", a->states_dev}, {"actions_dev", a->actions_dev}, {"next_states_dev", a->next_states_dev},
+      {"rewards_dev", a->rewards_dev}, {"dones_dev", a->dones_dev}, {"workspace_dev", a->workspace_dev}};
+  for (const auto &b : bufs)
+    if (!b.p) return fail(ARMENV_EINVAL, "%s: %s is NULL", fn, b.name);
+  if (!al16(a->workspace_dev)) return fail(ARMENV_EINVAL, "%s: workspace_dev is not 16-byte aligned", fn);
+  if (a->workspace_bytes < need)
+    return fail(ARMENV_EINVAL, "%s: workspace_bytes %lld, need %lld (%s)", fn, (long long)a->workspace_bytes, (long long)need, ws_fn);
+  return ARMENV_OK;
+}
+
+// DADDPG's workspace layout in floats (64-float boundaries, as Ws)
+struct WsD {
+  int64_t B, S;
+  int64_t ta1[2], ta2[2], tq1[2], tq2[2], h1, h2, d2, d1, ah1, ah2;   // [B][H] each; [2]: target actor / proposal 1 and 2
+  int64_t a2[2], api, tanh_a, du, d3, loss_rows;
+  int64_t pW3, pW2, pW1;                              // critic partials [S][rows][ld]
+  int64_t pa3, pa2, pa1;                              // actor partials, in the same slices
+  int64_t split_stride;
+  int64_t total;
+};
+
+WsD daddpg_layout(int64_t B) {
+  WsD w{};
+  w.B = B;
+  w.S = (B + LRN_KSPLIT - 1) / LRN_KSPLIT;
+  const int64_t H = LRN_H, BH = up64(B * H);
+  int64_t o = 0;
+  auto take = [&](int64_t n) { const int64_t r = o; o += up64(n); return r; };
+  for (int i = 0; i < 2; ++i) { w.ta1[i] = take(BH); w.ta2[i] = take(BH); w.tq1[i] = take(BH); w.tq2[i] = take(BH); }
+  w.h1 = take(BH); w.h2 = take(BH); w.d2 = take(BH); w.d1 = take(BH); w.ah1 = take(BH); w.ah2 = take(BH);
+  w.a2[0] = take(3 * B); w.a2[1] = take(3 * B); w.api = take(3 * B); w.tanh_a = take(3 * B); w.du = take(3 * B);
+  w.d3 = take(B); w.loss_rows = take(B);
+  // one partial slice holds the critic's W3 | b3 [1][H+1], W2 | b2 [H][H+1], W1 | b1 [H][16] OR the actor's W3 | b3 [3][H+1], ...:
+  // the two never live at the same time (the critic's are consumed by its Adam launch before the actor's are written), and with ONE
+  // critic the actor's slice is the larger -- the slice is the larger of the two
+  int64_t qc = 0, qa = 0;
+  auto sub = [](int64_t &q, int64_t n) { const int64_t r = q; q += up64(n); return r; };
+  w.pW3 = sub(qc, H + 1); w.pW2 = sub(qc, H * (H + 1)); w.pW1 = sub(qc, H * kW1Ld);
+  w.pa3 = sub(qa, 3 * (H + 1)); w.pa2 = sub(qa, H * (H + 1)); w.pa1 = sub(qa, H * kW1Ld);
+  w.split_stride = qc > qa ? qc : qa;
+  const int64_t part = take(w.S * w.split_stride);
+  w.pW3 += part; w.pW2 += part; w.pW1 += part;
+  w.pa3 += part; w.pa2 += part; w.pa1 += part;
+  w.total = o;
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -174,41 +261,21 @@ int64_t armenv_td3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_
 
 int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
   static const char *fn = "armenv_td3_update";
-  if (!a) return fail(ARMENV_EINVAL, "%s: args is NULL", fn);
-  if (a->device < 0) return fail(ARMENV_EINVAL, "%s: device %d", fn, a->device);
-  if (a->state_dim < 1 || a->state_dim > 12) return fail(ARMENV_EINVAL, "%s: state_dim %d outside 1..12", fn, a->state_dim);
-  if (a->action_dim != LRN_A) return fail(ARMENV_EINVAL, "%s: action_dim %d; the fused update is built for 3", fn, a->action_dim);
-  if (a->hidden_dim != LRN_H) return fail(ARMENV_EINVAL, "%s: hidden_dim %d; the fused update is built for %d", fn, a->hidden_dim, LRN_H);
-  if (a->batch < 1 || a->batch > kMaxBatch) return fail(ARMENV_EINVAL, "%s: batch %lld outside 1..%lld", fn, (long long)a->batch, (long long)kMaxBatch);
+  LRN_TRY(check_sizes(fn, a));
   if (a->with_actor != 0 && a->with_actor != 1) return fail(ARMENV_EINVAL, "%s: with_actor must be 0 or 1", fn);
   if (a->critic_step < 1) return fail(ARMENV_EINVAL, "%s: critic_step must be >= 1", fn);
   if (a->with_actor && a->actor_step < 1) return fail(ARMENV_EINVAL, "%s: actor_step must be >= 1", fn);
-  const struct { const char *name; float v; bool ok; } hp[] = {
+  const NamedF hp[] = {
       {"action_bound", a->action_bound, a->action_bound > 0.f}, {"gamma", a->gamma, a->gamma >= 0.f && a->gamma <= 1.f},
       {"tau", a->tau, a->tau >= 0.f && a->tau <= 1.f}, {"policy_noise", a->policy_noise, a->policy_noise >= 0.f},
       {"noise_clip", a->noise_clip, a->noise_clip >= 0.f}, {"actor_lr", a->actor_lr, a->actor_lr >= 0.f},
       {"critic_lr", a->critic_lr, a->critic_lr >= 0.f}, {"beta1", a->beta1, a->beta1 >= 0.f && a->beta1 < 1.f},
       {"beta2", a->beta2, a->beta2 >= 0.f && a->beta2 < 1.f}, {"eps", a->eps, a->eps > 0.f}};
-  for (const auto &h : hp)
-    if (!std::isfinite(h.v) || !h.ok) return fail(ARMENV_EINVAL, "%s: %s = %g out of range", fn, h.name, (double)h.v);
-  const struct { const char *name; const ArmEnvMlpRW *m; } nets[] = {
+  const NamedNet nets[] = {
       {"actor", &a->actor}, {"q1", &a->q1}, {"q2", &a->q2}, {"target_actor", &a->target_actor}, {"target_q1", &a->target_q1},
       {"target_q2", &a->target_q2}, {"actor_m", &a->actor_m}, {"actor_v", &a->actor_v}, {"q1_m", &a->q1_m}, {"q1_v", &a->q1_v},
       {"q2_m", &a->q2_m}, {"q2_v", &a->q2_v}};
-  for (const auto &n : nets) {
-    if (!mlp_ok(*n.m)) return fail(ARMENV_EINVAL, "%s: %s has a NULL pointer", fn, n.name);
-    if (!mlp_aligned(*n.m)) return fail(ARMENV_EINVAL, "%s: %s has a pointer that is not 16-byte aligned", fn, n.name);
-  }
-  const struct { const char *name; const void *p; } bufs[] = {
-      {"states_dev", a->states_dev}, {"actions_dev", a->actions_dev}, {"next_states_dev", a->next_states_dev},
-      {"rewards_dev", a->rewards_dev}, {"dones_dev", a->dones_dev}, {"workspace_dev", a->workspace_dev}};
-  for (const auto &b : bufs)
-    if (!b.p) return fail(ARMENV_EINVAL, "%s: %s is NULL", fn, b.name);
-  if (!al16(a->workspace_dev)) return fail(ARMENV_EINVAL, "%s: workspace_dev is not 16-byte aligned", fn);
-  const int64_t need = armenv_td3_workspace_bytes(a->state_dim, a->hidden_dim, a->batch);
-  if (a->workspace_bytes < need)
-    return fail(ARMENV_EINVAL, "%s: workspace_bytes %lld, need %lld (armenv_td3_workspace_bytes)", fn, (long long)a->workspace_bytes,
-                (long long)need);
+  LRN_TRY(check_buffers(fn, a, hp, nets, armenv_td3_workspace_bytes(a->state_dim, a->hidden_dim, a->batch), "armenv_td3_workspace_bytes"));
 
   DeviceGuard guard_(a->device);
   if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
@@ -278,7 +345,7 @@ int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
     for (int i = 0; i < 2; ++i)
       adam_tensors(P, *Q[i], i ? a->q2_m : a->q1_m, i ? a->q2_v : a->q1_v, *TQ[i], K1, 1, ws + w.pW1[i], ws + w.pW2[i], ws + w.pW3[i]);
     P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = a->with_actor;
-    P.loss_rows = ws + w.loss_rows; P.B = B; P.inv_b = 1.0f / (float)B; P.loss = a->loss_dev;
+    P.loss_rows = ws + w.loss_rows; P.loss_cols = 2; P.B = B; P.inv_b = 1.0f / (float)B; P.loss = a->loss_dev;
     LRN_TRY(launch_adam(P, a->critic_lr, a->critic_step, a, s));
   }
   if (!a->with_actor) return ARMENV_OK;
@@ -310,6 +377,127 @@ int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
   // 16: actor Adam + the target actor's soft update
   AdamArgs P{};
   adam_tensors(P, a->actor, a->actor_m, a->actor_v, a->target_actor, D, LRN_A, ws + w.pa1, ws + w.pa2, ws + w.pa3);
+  P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = 1;
+  return launch_adam(P, a->actor_lr, a->actor_step, a, s);
+}
+
+int64_t armenv_daddpg_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch) {
+  if (state_dim < 1 || state_dim > 12 || hidden_dim != LRN_H || batch < 1 || batch > kMaxBatch) return -1;
+  return daddpg_layout(batch).total * (int64_t)sizeof(float);
+}
+
+int armenv_daddpg_update(const ArmEnvDaddpgArgs *a, void *stream) {
+  static const char *fn = "armenv_daddpg_update";
+  LRN_TRY(check_sizes(fn, a));
+  if (a->update_actor != 1 && a->update_actor != 2) return fail(ARMENV_EINVAL, "%s: update_actor %d must be 1 or 2", fn, a->update_actor);
+  if (a->critic_step < 1) return fail(ARMENV_EINVAL, "%s: critic_step must be >= 1", fn);
+  if (a->actor_step < 1) return fail(ARMENV_EINVAL, "%s: actor_step must be >= 1", fn);
+  const NamedF hp[] = {
+      {"action_bound", a->action_bound, a->action_bound > 0.f}, {"gamma", a->gamma, a->gamma >= 0.f && a->gamma <= 1.f},
+      {"tau", a->tau, a->tau >= 0.f && a->tau <= 1.f}, {"actor_lr", a->actor_lr, a->actor_lr >= 0.f},
+      {"critic_lr", a->critic_lr, a->critic_lr >= 0.f}, {"beta1", a->beta1, a->beta1 >= 0.f && a->beta1 < 1.f},
+      {"beta2", a->beta2, a->beta2 >= 0.f && a->beta2 < 1.f}, {"eps", a->eps, a->eps > 0.f}};
+  const NamedNet nets[] = {
+      {"actor1", &a->actor1}, {"actor2", &a->actor2}, {"critic", &a->critic}, {"target_actor1", &a->target_actor1},
+      {"target_actor2", &a->target_actor2}, {"target_critic", &a->target_critic}, {"actor1_m", &a->actor1_m},
+      {"actor1_v", &a->actor1_v}, {"actor2_m", &a->actor2_m}, {"actor2_v", &a->actor2_v}, {"critic_m", &a->critic_m},
+      {"critic_v", &a->critic_v}};
+  LRN_TRY(check_buffers(fn, a, hp, nets, armenv_daddpg_workspace_bytes(a->state_dim, a->hidden_dim, a->batch),
+                        "armenv_daddpg_workspace_bytes"));
+
+  DeviceGuard guard_(a->device);
+  if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int D = a->state_dim, K1 = D + LRN_A, H = LRN_H;
+  const int64_t B = a->batch;
+  const WsD w = daddpg_layout(B);
+  float *ws = static_cast<float *>(a->workspace_dev);
+  const bool second = a->update_actor == 2;
+  const ArmEnvMlpRW &Q = a->critic, &TQ = a->target_critic;
+  const ArmEnvMlpRW &act = second ? a->actor2 : a->actor1, &t_act = second ? a->target_actor2 : a->target_actor1;
+  const ArmEnvMlpRW *TA[2] = {&a->target_actor1, &a->target_actor2};
+  const Feat s2_only = feat(a->next_states_dev, D, D, B);
+  Launcher L;
+
+  // 1-2: layers 1 and 2 of both target actors, the critic and actor k
+  for (int i = 0; i < 2; ++i) L.forward(s2_only, D, TA[i]->W1, TA[i]->b1, ws + w.ta1[i], B);
+  L.forward(feat2(a->states_dev, D, a->actions_dev, LRN_A, K1, B), K1, Q.W1, Q.b1, ws + w.h1, B);
+  L.forward(feat(a->states_dev, D, D, B), D, act.W1, act.b1, ws + w.ah1, B);
+  LRN_TRY(L.launch(s));
+  for (int i = 0; i < 2; ++i) L.forward(feat(ws + w.ta1[i], H, H, B), H, TA[i]->W2, TA[i]->b2, ws + w.ta2[i], B);
+  L.forward(feat(ws + w.h1, H, H, B), H, Q.W2, Q.b2, ws + w.h2, B);
+  L.forward(feat(ws + w.ah1, H, H, B), H, act.W2, act.b2, ws + w.ah2, B);
+  LRN_TRY(L.launch(s));
+
+  // 3: the three actor heads
+  DaddpgActorHeadArgs ah{};
+  ah.B = B; ah.bound = a->action_bound;
+  for (int i = 0; i < 2; ++i) { ah.h2[i] = ws + w.ta2[i]; ah.W3[i] = TA[i]->W3; ah.b3[i] = TA[i]->b3; ah.a[i] = ws + w.a2[i]; }
+  ah.h2[2] = ws + w.ah2; ah.W3[2] = act.W3; ah.b3[2] = act.b3; ah.a[2] = ws + w.api; ah.tanh_out = ws + w.tanh_a;
+  const unsigned row_blocks = grid_for(B, 4);
+  hipLaunchKernelGGL(daddpg_actor_head_kernel, dim3(row_blocks * 3u), dim3(256), 0, s, ah);
+  HIP_TRY(hipGetLastError());
+
+  // 4-5: the ONE target critic over both proposals
+  for (int i = 0; i < 2; ++i) L.forward(feat2(a->next_states_dev, D, ws + w.a2[i], LRN_A, K1, B), K1, TQ.W1, TQ.b1, ws + w.tq1[i], B);
+  LRN_TRY(L.launch(s));
+  for (int i = 0; i < 2; ++i) L.forward(feat(ws + w.tq1[i], H, H, B), H, TQ.W2, TQ.b2, ws + w.tq2[i], B);
+  LRN_TRY(L.launch(s));
+
+  // 6: target, loss rows, critic deltas
+  DaddpgCriticHeadArgs ch{};
+  ch.B = B; ch.gamma = a->gamma; ch.inv_b = 1.0f / (float)B; ch.rewards = a->rewards_dev; ch.dones = a->dones_dev;
+  ch.t_h2[0] = ws + w.tq2[0]; ch.t_h2[1] = ws + w.tq2[1]; ch.t_W3 = TQ.W3; ch.t_b3 = TQ.b3;
+  ch.h2 = ws + w.h2; ch.W3 = Q.W3; ch.b3 = Q.b3; ch.d3 = ws + w.d3; ch.d2 = ws + w.d2; ch.loss_rows = ws + w.loss_rows;
+  hipLaunchKernelGGL(daddpg_critic_head_kernel, dim3(row_blocks), dim3(256), 0, s, ch);
+  HIP_TRY(hipGetLastError());
+
+  // 7-8: critic backward and weight-gradient partials
+  L.backward(ws + w.d2, Q.W2, ws + w.h1, ws + w.d1, B);
+  L.wgrad(ws + w.d3, 1, feat(ws + w.h2, H, H, B, 1), H, ws + w.pW3, H + 1, B, w.split_stride);
+  L.wgrad(ws + w.d2, H, feat(ws + w.h1, H, H, B, 1), H, ws + w.pW2, H + 1, B, w.split_stride);
+  LRN_TRY(L.launch(s));
+  L.wgrad(ws + w.d1, H, feat2(a->states_dev, D, a->actions_dev, LRN_A, K1, B, 1), K1, ws + w.pW1, kW1Ld, B, w.split_stride);
+  LRN_TRY(L.launch(s));
+
+  // 9: critic Adam (+ loss, + the target critic's soft update when actor 2 is stepped)
+  {
+    AdamArgs P{};
+    adam_tensors(P, Q, a->critic_m, a->critic_v, TQ, K1, 1, ws + w.pW1, ws + w.pW2, ws + w.pW3);
+    P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = second;
+    P.loss_rows = ws + w.loss_rows; P.loss_cols = 1; P.B = B; P.inv_b = 1.0f / (float)B; P.loss = a->loss_dev;
+    LRN_TRY(launch_adam(P, a->critic_lr, a->critic_step, a, s));
+  }
+
+  // 10-12: critic(s, actor_k(s)) with the stepped critic and its backward to the critic's input; c1 / dc2 / dc1 / da2 / da1 reuse
+  // the target path's buffers
+  float *c1 = ws + w.ta1[0], *dc2 = ws + w.ta2[0], *dc1 = ws + w.tq1[0], *da2 = ws + w.tq1[1], *da1 = ws + w.tq2[0];
+  L.forward(feat2(a->states_dev, D, ws + w.api, LRN_A, K1, B), K1, Q.W1, Q.b1, c1, B);
+  LRN_TRY(L.launch(s));
+  L.forward(feat(c1, H, H, B), H, Q.W2, Q.b2, dc2, B, EPI_DRELU_W, Q.W3, -1.0f / (float)B);
+  LRN_TRY(L.launch(s));
+  L.backward(dc2, Q.W2, c1, dc1, B);
+  LRN_TRY(L.launch(s));
+
+  // 13: through cat -> tanh -> actor k's fc3
+  ActorBackArgs ab{};
+  ab.B = B; ab.in_dim = K1; ab.state_dim = D; ab.bound = a->action_bound; ab.dc1 = dc1; ab.Wq1 = Q.W1;
+  ab.tanh_a = ws + w.tanh_a; ab.h2 = ws + w.ah2; ab.W3 = act.W3; ab.du = ws + w.du; ab.da2 = da2;
+  hipLaunchKernelGGL(actor_back_kernel, dim3(row_blocks), dim3(256), 0, s, ab);
+  HIP_TRY(hipGetLastError());
+
+  // 14-15: actor k's backward and weight-gradient partials (the critic's partials are consumed: same slices)
+  L.backward(da2, act.W2, ws + w.ah1, da1, B);
+  L.wgrad(ws + w.du, LRN_A, feat(ws + w.ah2, H, H, B, 1), H, ws + w.pa3, H + 1, B, w.split_stride);
+  L.wgrad(da2, H, feat(ws + w.ah1, H, H, B, 1), H, ws + w.pa2, H + 1, B, w.split_stride);
+  LRN_TRY(L.launch(s));
+  L.wgrad(da1, H, feat(a->states_dev, D, D, B, 1), D, ws + w.pa1, kW1Ld, B, w.split_stride);
+  LRN_TRY(L.launch(s));
+
+  // 16: actor k's Adam + its target's soft update
+  AdamArgs P{};
+  adam_tensors(P, act, second ? a->actor2_m : a->actor1_m, second ? a->actor2_v : a->actor1_v, t_act, D, LRN_A, ws + w.pa1, ws + w.pa2,
+               ws + w.pa3);
   P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = 1;
   return launch_adam(P, a->actor_lr, a->actor_step, a, s);
 }

@@ -35,7 +35,8 @@ extern "C" {
 #endif
 
 #define ARMENV_NJ 7
-#define ARMENV_ABI_VERSION 7   /* 7: + armenv_td3_update, armenv_td3_workspace_bytes, ArmEnvMlpRW, ArmEnvTd3Args;
+#define ARMENV_ABI_VERSION 8   /* 8: + armenv_daddpg_update, armenv_daddpg_workspace_bytes, ArmEnvDaddpgArgs;
+                                  7: + armenv_td3_update, armenv_td3_workspace_bytes, ArmEnvMlpRW, ArmEnvTd3Args;
                                   6: + armenv_set_policy_daddpg, armenv_episode_returns_f32, ARMENV_POLICY_DADDPG; ArmEnvConfig unchanged since 5 */
 
 enum {
@@ -475,6 +476,43 @@ typedef struct ArmEnvTd3Args {
 /* Bytes of workspace armenv_td3_update needs for (state_dim, hidden_dim, batch); -1 for unsupported sizes. */
 int64_t armenv_td3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch);
 int armenv_td3_update(const ArmEnvTd3Args *args, void *stream);
+
+/* ---- fused DADDPG learner: one DADDPG_MLP.update (the reference's algo/DADDPG/DADDPG_mlp.py:117-171), the reference's DEFAULT
+ * agent (config.py:33), over two actors (fc1-3, tanh x action_bound) and ONE critic over cat(s, a) (fc1-3), hidden_dim 256:
+ *   a2_k   = target_actor_k(s2), k = 1, 2 (no target-policy noise, no clamp)
+ *   target = r + (1 - d) gamma min(target_critic(s2, a2_1), target_critic(s2, a2_2))
+ *   critic: loss = mse(critic(s, a), target), one Adam step
+ *   actor k = update_actor (1 when the caller's total_it, incremented before the update, is even; 2 when odd, DADDPG_mlp.py:119):
+ *   loss -mean(critic(s, actor_k(s))) with the critic AFTER its step, one Adam step on actor k, then the Polyak soft update (tau)
+ *   of target_actor_k -- and, when k == 2, of the target critic (DADDPG_mlp.py:160-168).
+ * Adam is torch.optim.Adam's: no weight decay, bias corrections 1 - beta^step from the 1-based step numbers passed in; three
+ * optimisers (critic, actor 1, actor 2), each with its own step counter.  Parameters, targets and moments are updated in place;
+ * the other actor, its target and its moments are not touched.
+ *
+ * Properties (as armenv_td3_update): every contraction runs on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32); batch sums are
+ * per-slice partials added in slice order (no atomics), so an update is bitwise reproducible run to run.  The call only enqueues
+ * kernels on `stream`: 16 launches; no allocation, no memset, no host synchronisation, so it can be captured into a graph.  All
+ * intermediates live in the caller's workspace (armenv_daddpg_workspace_bytes).  Every argument is validated before any HIP call:
+ * a bad one returns ARMENV_EINVAL and armenv_last_error() names the field. */
+typedef struct ArmEnvDaddpgArgs {
+  int32_t device, state_dim, action_dim, hidden_dim;   /* state_dim 1..12 (6 reach, 9 push / pick), action_dim 3, hidden_dim 256 */
+  int64_t batch;                                       /* B >= 1, any size up to 2^20 */
+  float action_bound, gamma, tau, actor_lr, critic_lr, beta1, beta2, eps;
+  int64_t critic_step;                                 /* 1-based Adam step number of THIS update: the critic's optimiser */
+  int64_t actor_step;                                  /* ... and the optimiser of the actor updated this call */
+  int32_t update_actor;                                /* 1 or 2 */
+  ArmEnvMlpRW actor1, actor2, critic, target_actor1, target_actor2, target_critic;
+  ArmEnvMlpRW actor1_m, actor1_v, actor2_m, actor2_v, critic_m, critic_v;   /* Adam moments, same shapes */
+  const float *states_dev, *actions_dev, *next_states_dev, *rewards_dev;   /* [B][state_dim], [B][3], [B][state_dim], [B] */
+  const uint8_t *dones_dev;                            /* [B] */
+  float *loss_dev;                                     /* nullable out: f32 scalar critic loss */
+  void *workspace_dev;                                 /* device, 16-byte aligned */
+  int64_t workspace_bytes;
+} ArmEnvDaddpgArgs;
+
+/* Bytes of workspace armenv_daddpg_update needs for (state_dim, hidden_dim, batch); -1 for unsupported sizes. */
+int64_t armenv_daddpg_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch);
+int armenv_daddpg_update(const ArmEnvDaddpgArgs *args, void *stream);
 
 /* Measurement aid (bench.py's roofline.valu.one_wave_per_simd; no reference counterpart): the interval at which SIMDs issue
  * independent 64-lane v_fma_f64 (precision 64) / v_fma_f32 (32) instructions when every SIMD of `device` holds
