@@ -97,6 +97,21 @@ class ArmEnvDaddpgArgs(C.Structure):
         + [("workspace_bytes", C.c_int64)])
 
 
+class ArmEnvDatd3Args(C.Structure):
+    _fields_ = (
+        [("device", C.c_int32), ("state_dim", C.c_int32), ("action_dim", C.c_int32), ("hidden_dim", C.c_int32), ("batch", C.c_int64)]
+        + [(k, C.c_float) for k in ("action_bound", "gamma", "tau", "policy_noise", "noise_clip", "actor_lr", "critic_lr",
+                                    "beta1", "beta2", "eps", "q_weight", "regularization_weight")]
+        + [("critic_step", C.c_int64), ("actor_step", C.c_int64), ("update_actor", C.c_int32), ("darc", C.c_int32),
+           ("seed", C.c_uint64), ("draw", C.c_uint64), ("noise_dev", C.c_void_p)]
+        + [(k, ArmEnvMlpRW) for k in ("actor1", "actor2", "critic1", "critic2", "target_actor1", "target_actor2", "target_critic1",
+                                      "target_critic2", "actor1_m", "actor1_v", "actor2_m", "actor2_v", "critic1_m", "critic1_v",
+                                      "critic2_m", "critic2_v")]
+        + [(k, C.c_void_p) for k in ("states_dev", "actions_dev", "next_states_dev", "rewards_dev", "dones_dev", "loss_dev",
+                                     "workspace_dev")]
+        + [("workspace_bytes", C.c_int64)])
+
+
 # every symbol include/armenv.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -130,6 +145,8 @@ SYMBOLS = {
     "armenv_td3_update": (C.c_int, [C.POINTER(ArmEnvTd3Args), _P]),
     "armenv_daddpg_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     "armenv_daddpg_update": (C.c_int, [C.POINTER(ArmEnvDaddpgArgs), _P]),
+    "armenv_datd3_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
+    "armenv_datd3_update": (C.c_int, [C.POINTER(ArmEnvDatd3Args), _P]),
     "armenv_probe_issue_rate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "armenv_probe_clock": (C.c_int, [C.c_int32, _P, C.POINTER(C.c_int32), _P]),
     "armenv_num_envs": (C.c_int64, [_P]),

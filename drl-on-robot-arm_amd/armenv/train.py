@@ -3,12 +3,15 @@ GPU -- fused-policy rollouts (armenv_rollout), trajectory store + HER batches (a
 success accounting (armenv_counters).  One iteration = `rollout_steps` env steps of `num_envs` envs followed by
 `updates` updates; the reference does 40 updates of 256 samples after every (<= 501-step) episode of its single env.
 The agent: `--algo td3` (train_reach_with_TD3's, main.py:165-231) or `--algo daddpg` -- opt.algo's default, what `run()` itself
-instantiates (config.py:33, main.py:93): two actors and one critic, take_action fused into the rollout kernel.
+instantiates (config.py:33, main.py:93): two actors and one critic, take_action fused into the rollout kernel; or `--algo datd3` /
+`--algo darc` -- two actors AND two critics (armenv.datd3), whose one loop "update" is one `train` = two reference updates on the
+batch, as the reference's run() counts them.
 
     python -m armenv.train --iterations 200
     python -m armenv.train --iterations 200 --algo daddpg
     python -m armenv.train --iterations 200 --learner hip      # the fused HIP TD3 update (armenv.fused_td3)
     python -m armenv.train --iterations 200 --algo daddpg --learner fused    # the agent's own fused HIP update (armenv.fused_daddpg)
+    python -m armenv.train --iterations 200 --algo datd3 --learner fused     # ... armenv.fused_datd3 (also --algo darc)
 """
 import argparse
 import json
@@ -19,12 +22,20 @@ import torch
 from . import envs
 from .replay import TrajectoryStore
 from .daddpg import DADDPG
+from .datd3 import DARC, DATD3
 from .fused_daddpg import FusedDADDPG
+from .fused_datd3 import FusedDARC, FusedDATD3
 from .fused_td3 import FusedTD3
 from .td3 import TD3
 
 
+ALGOS = ("td3", "daddpg", "datd3", "darc")
+_TORCH = dict(td3=TD3, daddpg=DADDPG, datd3=DATD3, darc=DARC)
+
+
 def _check_learner(algo, learner):
+    if algo not in ALGOS:
+        raise ValueError("algo must be one of %s" % ", ".join(ALGOS))
     if learner not in ("torch", "hip", "fused"):
         raise ValueError("learner must be 'torch', 'hip' or 'fused'")
     if learner == "hip" and algo != "td3":
@@ -36,10 +47,12 @@ def _make_agent(algo, learner, state_dim, action_bound, device, batch_size, use_
     if learner in ("hip", "fused"):       # "hip": FusedTD3 (td3 only); "fused": the agent's own fused update
         if algo == "daddpg":
             agent = FusedDADDPG(state_dim, 3, action_bound, device=device)
+        elif algo in ("datd3", "darc"):
+            agent = (FusedDARC if algo == "darc" else FusedDATD3)(state_dim, 3, action_bound, device=device, seed=seed)
         else:
             agent = FusedTD3(state_dim, 3, action_bound, device=device, seed=seed)
         return agent, agent.batch_buffers(batch_size), False
-    agent = (DADDPG if algo == "daddpg" else TD3)(state_dim, 3, action_bound, device=device)   # getattr(algo, opt.algo)(...)
+    agent = _TORCH[algo](state_dim, 3, action_bound, device=device)   # getattr(algo, opt.algo)(...)
     static = agent.capture(batch_size) if use_graphs else None     # TD3 update as hipGraphs: launch-bound otherwise
     return agent, static, use_graphs
 
@@ -48,7 +61,8 @@ def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, bat
                 device="cuda:0", actor_kind="actor_f16x3", expl_sigma=0.7 * 0.98, log_every=10, log=print,
                 window_steps=1536, minimal_episodes=5, max_steps=500, use_graphs=True, algo="td3", learner="torch"):
     # learner="hip": the TD3 update is libarmenv's fused one (armenv.fused_td3.FusedTD3), issued directly: no capture, no graph.
-    # learner="fused": the agent's own fused update -- FusedTD3 for td3, armenv.fused_daddpg.FusedDADDPG for daddpg.
+    # learner="fused": the agent's own fused update -- FusedTD3 for td3, armenv.fused_daddpg.FusedDADDPG for daddpg,
+    # armenv.fused_datd3.FusedDATD3 / FusedDARC for datd3 / darc.
     # use_graphs: the agent's update replayed from hipGraphs (GraphedLearner.capture): the update is ~130 small kernels, launch-bound
     # when issued one by one (160 iterations: 7 s against 14 s).  Round 6 found the replayed updates no longer learning and why: a
     # hipMemsetAsync captured into a hipGraph works on the first replay only on this ROCm build, torch's multi-block reductions
@@ -70,6 +84,9 @@ def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, bat
         # take_action + exploration noise + step, fused (main.py:114-124)
         if algo == "daddpg":
             env.set_policy_daddpg(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=expl_sigma, noise_clip=action_bound)
+        elif algo in ("datd3", "darc"):
+            install = env.set_policy_darc if algo == "darc" else env.set_policy_datd3
+            install(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=expl_sigma, noise_clip=action_bound)
         else:
             env.set_policy(actor_kind, action_bound=action_bound, noise_sigma=expl_sigma, noise_clip=action_bound,
                            actor_state_dict=agent.actor_state_dict())
@@ -122,6 +139,9 @@ def train_push(num_envs=1024, iterations=300, rollout_steps=32, updates=48, batc
     for it in range(iterations):
         if algo == "daddpg":
             env.set_policy_daddpg(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=action_bound * 0.98, noise_clip=1e9)
+        elif algo in ("datd3", "darc"):
+            install = env.set_policy_darc if algo == "darc" else env.set_policy_datd3
+            install(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=action_bound * 0.98, noise_clip=1e9)
         else:
             env.set_policy(actor_kind, action_bound=action_bound, noise_sigma=action_bound * 0.98, noise_clip=1e9,
                            actor_state_dict=agent.actor_state_dict())
@@ -164,10 +184,10 @@ def main():
     ap.add_argument("--window-steps", type=int, default=1536)
     ap.add_argument("--max-steps", type=int, default=500, help="opt.max_steps_one_episode")
     ap.add_argument("--graphs", type=int, default=1, help="1: the agent's updates replayed from hipGraphs (default); 0: issued eagerly")
-    ap.add_argument("--algo", default="td3", choices=["td3", "daddpg"], help="the agent (config.py:33's default is DADDPG_MLP)")
+    ap.add_argument("--algo", default="td3", choices=list(ALGOS), help="the agent (config.py:33's default is DADDPG_MLP)")
     ap.add_argument("--learner", default="torch", choices=["torch", "hip", "fused"],
                     help="torch: the agent's update in torch (default); hip: libarmenv's fused TD3 update (--algo td3 only); "
-                         "fused: the agent's own fused HIP update (FusedTD3 or FusedDADDPG)")
+                         "fused: the agent's own fused HIP update (FusedTD3, FusedDADDPG, FusedDATD3 or FusedDARC)")
     a = ap.parse_args()
     if a.task != "reach":
         train_push(a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed, actor_kind=a.actor,

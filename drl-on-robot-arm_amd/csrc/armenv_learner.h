@@ -1,6 +1,7 @@
 // armenv_learner.h -- kernels of the fused learner updates (armenv_learner.hip): armenv_td3_update, TD3_MLP.train (the reference's
-// algo/TD3/TD3_mlp.py:114-161), and armenv_daddpg_update, DADDPG_MLP.update (algo/DADDPG/DADDPG_mlp.py:117-171), over the networks
-// of net_mlp.py, hidden width 256, exact f32.
+// algo/TD3/TD3_mlp.py:114-161), armenv_daddpg_update, DADDPG_MLP.update (algo/DADDPG/DADDPG_mlp.py:117-171), and armenv_datd3_update,
+// DATD3_MLP.update / DARC_MLP.update (algo/DATD3/DATD3_mlp.py:146-211, algo/DARC/DARC_mlp.py:140-222), over the networks of
+// net_mlp.py, hidden width 256, exact f32.
 //
 // Three kinds of kernel, each launched over a LIST of independent problems so that every stage of the update is one launch:
 //   gemm_kernel        C = A . B on v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: no xf32 on gfx950).  A 64 x 64 output tile
@@ -18,6 +19,9 @@
 //                      the Polyak soft update of the matching target network folded in, and (critic) the loss.
 // The DADDPG update shares gemm_kernel, actor_back_kernel and adam_kernel; its two per-row heads are daddpg_actor_head_kernel and
 // daddpg_critic_head_kernel (two actors and their targets, ONE critic, no target-policy noise).
+// The DATD3 / DARC update shares the same three; its heads are datd3_actor_head_kernel (both target actors' proposals under ONE noise
+// draw per row, and the stepped actor's action) and datd3_critic_head_kernel (two target critics, the stepped critic, and with `darc`
+// the mixed target and the pull towards the other critic).
 // No kernel uses atomics, scratch or a memset; nothing is allocated: all intermediates live in the caller's workspace.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -339,6 +343,120 @@ __global__ __launch_bounds__(256) void daddpg_critic_head_kernel(DaddpgCriticHea
   reinterpret_cast<float4 *>(P.d2 + b * LRN_H)[lane] = d;
 }
 
+struct Datd3ActorHeadArgs {
+  int64_t B;
+  float bound, policy_noise, noise_clip;
+  const float *noise;        // nullable [B][3] standard normals in place of the draw
+  uint64_t seed, draw;
+  // target rows: a2_j = clamp(bound tanh(h2_j W3_j^T + b3_j) + clamp(z policy_noise, +-noise_clip), +-bound), j = 0, 1, ONE z per row
+  const float *t_h2[2], *t_W3[2], *t_b3[2];
+  float *a2[2];              // out [B][3] each
+  // actor rows: a = bound tanh(h2 W3^T + b3) of the stepped actor over s, and tanh kept for the backward pass
+  const float *h2, *W3, *b3;
+  float *a, *tanh_out;
+};
+
+// blocks [0, ceil(B / 4)): target rows, one wave computes BOTH proposals of its row from one noise draw; the next ceil(B / 4): actor rows
+__global__ __launch_bounds__(256) void datd3_actor_head_kernel(Datd3ActorHeadArgs P) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nb = (P.B + 3) / 4;
+  const bool actor = (int64_t)blockIdx.x >= nb;
+  const int64_t b = ((int64_t)blockIdx.x - (actor ? nb : 0)) * 4 + (threadIdx.x >> 6);
+  if (b >= P.B) return;
+  if (actor) {
+    const float4 h = row4(P.h2, b, lane);
+    float u[LRN_A];
+#pragma unroll
+    for (int j = 0; j < LRN_A; ++j) u[j] = wave_sum(dot4(h, row4(P.W3, j, lane))) + P.b3[j];
+    if (lane != 0) return;
+#pragma unroll
+    for (int j = 0; j < LRN_A; ++j) {
+      const float th = tanhf(u[j]);
+      P.tanh_out[b * LRN_A + j] = th;
+      P.a[b * LRN_A + j] = th * P.bound;
+    }
+    return;
+  }
+  float u[2][LRN_A];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const float4 h = row4(P.t_h2[i], b, lane);
+#pragma unroll
+    for (int j = 0; j < LRN_A; ++j) u[i][j] = wave_sum(dot4(h, row4(P.t_W3[i], j, lane))) + P.t_b3[i][j];
+  }
+  if (lane != 0) return;
+  float z[4];
+  if (P.noise) {
+#pragma unroll
+    for (int j = 0; j < LRN_A; ++j) z[j] = P.noise[b * LRN_A + j];
+  } else {
+    // Philox4x32-10 keyed by seed, counter (row, draw): independent of launch geometry
+    uint32_t c[4] = {(uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)P.draw, (uint32_t)(P.draw >> 32)};
+    philox4x32_10(c, (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
+    box_muller(c[0], c[1], z[0], z[1]);
+    box_muller(c[2], c[3], z[2], z[3]);
+  }
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) {
+    const float nz = fminf(fmaxf(z[j] * P.policy_noise, -P.noise_clip), P.noise_clip);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const float v = tanhf(u[i][j]) * P.bound + nz;
+      P.a2[i][b * LRN_A + j] = fminf(fmaxf(v, -P.bound), P.bound);
+    }
+  }
+}
+
+struct Datd3CriticHeadArgs {
+  int64_t B;
+  float gamma, inv_b;
+  int darc;
+  float w_min, w_max, reg;                     // darc: q_weight, 1 - q_weight, regularization_weight
+  const float *rewards;
+  const uint8_t *dones;
+  const float *t_h2[2], *t_W3[2], *t_b3[2];    // target critic j's last hidden layer over cat(s2, a2_j) and its fc3
+  const float *h2, *W3, *b3;                   // the stepped critic's, over cat(s, a)
+  const float *o_h2, *o_W3, *o_b3;             // darc: the other critic's, over cat(s, a)
+  float *d3;                                   // out [B]: dLoss / dq
+  float *d2;                                   // out [B][H]: (d3 W3) * relu'(h2)
+  float *loss_rows;                            // out [B]: (q - target)^2; darc [B][2]: and (q - q_other)^2
+};
+
+// target = r + (1 - d) gamma T, T = min(tq1, tq2) (darc: w_min T + w_max T); loss = mse(q, target) (darc: + reg mse(q, q_other)) and
+// its deltas, one wave per row
+__global__ __launch_bounds__(256) void datd3_critic_head_kernel(Datd3CriticHeadArgs P) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= P.B) return;
+  const float tq0 = wave_sum(dot4(row4(P.t_h2[0], b, lane), row4(P.t_W3[0], 0, lane))) + P.t_b3[0][0];
+  const float tq1 = wave_sum(dot4(row4(P.t_h2[1], b, lane), row4(P.t_W3[1], 0, lane))) + P.t_b3[1][0];
+  const float4 h = row4(P.h2, b, lane), w = row4(P.W3, 0, lane);
+  const float q = wave_sum(dot4(h, w)) + P.b3[0];
+  float t = fminf(tq0, tq1);
+  if (P.darc) t = P.w_min * t + P.w_max * t;
+  const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
+  const float target = P.rewards[b] + notdone * P.gamma * t;
+  const float e = q - target;
+  float d3 = 2.0f * e * P.inv_b;
+  if (P.darc) {
+    const float eo = q - (wave_sum(dot4(row4(P.o_h2, b, lane), row4(P.o_W3, 0, lane))) + P.o_b3[0]);
+    d3 += P.reg * (2.0f * eo * P.inv_b);
+    if (lane == 0) {
+      P.loss_rows[2 * b] = e * e;
+      P.loss_rows[2 * b + 1] = eo * eo;
+    }
+  } else if (lane == 0) {
+    P.loss_rows[b] = e * e;
+  }
+  if (lane == 0) P.d3[b] = d3;
+  float4 d;
+  d.x = h.x > 0.f ? d3 * w.x : 0.f;
+  d.y = h.y > 0.f ? d3 * w.y : 0.f;
+  d.z = h.z > 0.f ? d3 * w.z : 0.f;
+  d.w = h.w > 0.f ? d3 * w.w : 0.f;
+  reinterpret_cast<float4 *>(P.d2 + b * LRN_H)[lane] = d;
+}
+
 struct ActorBackArgs {
   int64_t B;
   int in_dim;            // state_dim + 3: row length of Q1's fc1 weight
@@ -400,7 +518,8 @@ struct AdamArgs {
   int soft;
   // the critic's launch also reduces the loss: one extra block after the elementwise ones
   const float *loss_rows;
-  int loss_cols;             // loss_rows is [B][loss_cols]: 2 (TD3's twin critic) or 1 (DADDPG's one critic)
+  int loss_cols;             // loss_rows is [B][loss_cols]: 2 (TD3's twin critic; DARC's two terms) or 1 (DADDPG's / DATD3's one)
+  float loss_w1;             // weight of column 1's mean: 1 (TD3), regularization_weight (DARC)
   int64_t B;
   float inv_b;
   float *loss;
@@ -410,7 +529,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs P) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t elem_blocks = ((int64_t)P.total + 255) / 256;
   if ((int64_t)blockIdx.x >= elem_blocks) {
-    // loss = mean((q1 - t)^2) + mean((q2 - t)^2) (one column: mean((q - t)^2)), summed in a fixed order
+    // loss = mean(column 0) + loss_w1 mean(column 1) (one column: its mean), each summed in a fixed order
     __shared__ float red[2][256];
     float s0 = 0.f, s1 = 0.f;
     if (P.loss_cols == 2) {
@@ -431,7 +550,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs P) {
       }
       __syncthreads();
     }
-    if (threadIdx.x == 0 && P.loss) P.loss[0] = P.loss_cols == 2 ? red[0][0] * P.inv_b + red[1][0] * P.inv_b : red[0][0] * P.inv_b;
+    if (threadIdx.x == 0 && P.loss) P.loss[0] = P.loss_cols == 2 ? red[0][0] * P.inv_b + P.loss_w1 * (red[1][0] * P.inv_b) : red[0][0] * P.inv_b;
     return;
   }
   if (e >= P.total) return;

@@ -1,6 +1,6 @@
-// armenv_learner.hip -- armenv_td3_update / armenv_td3_workspace_bytes and armenv_daddpg_update / armenv_daddpg_workspace_bytes
-// (include/armenv.h): argument checks, workspace layouts and the launch sequences of the fused TD3 and DADDPG updates over the
-// kernels of armenv_learner.h.
+// armenv_learner.hip -- armenv_td3_update / armenv_td3_workspace_bytes, armenv_daddpg_update / armenv_daddpg_workspace_bytes and
+// armenv_datd3_update / armenv_datd3_workspace_bytes (include/armenv.h): argument checks, workspace layouts and the launch sequences
+// of the fused TD3, DADDPG and DATD3 / DARC updates over the kernels of armenv_learner.h.
 //
 // TD3 launches (B rows, H = 256, D = state_dim, K1 = D + 3); every stage is one launch over all its independent problems:
 //   1 gemm    layer 1: target actor (s2), critic Q1 and Q2 (cat(s, a)), actor (s) when with_actor
@@ -32,6 +32,21 @@
 //   8 gemm    dW1 | db1 partials
 //   9 adam    critic (6 tensors) + the loss; update_actor == 2: the target critic's soft update (the critic is final by then)
 //  10-16      as TD3's 10-16 with the ONE critic in Q1's place and actor k in the actor's; 16 soft-updates target actor k only
+//
+// DATD3 / DARC launches (two actors, TWO critics; critic k and actor k = update_actor are stepped, `other` = 3 - k), always 16:
+//   1 gemm    layer 1: target actors 1 and 2 (s2), critic k (cat(s, a)), actor k (s); darc: critic `other` (cat(s, a)) as a fifth problem
+//   2 gemm    layer 2 of the same nets
+//   3 head    target actors' fc3 + ONE noise draw per row, clamped -> a2_1, a2_2; actor k's fc3 -> a = actor_k(s) and its tanh
+//   4 gemm    layer 1 of target critic 1 over cat(s2, a2_1) and of target critic 2 over cat(s2, a2_2)
+//   5 gemm    layer 2 of the same two problems
+//   6 head    T = min(tq1, tq2) (darc: q_weight T + (1 - q_weight) T), target = r + (1 - d) gamma T, critic k's fc3 (darc: and the
+//             other's), loss row(s), d3 = 2/B (q - target) (darc: + 2 w/B (q - q_other)) and d2 = (d3 W3) relu'(h2)
+//   7 gemm    d1 = (d2 W2) relu'(h1); dW3 | db3 and dW2 | db2 partials of critic k
+//   8 gemm    dW1 | db1 partials
+//   9 adam    critic k (6 tensors) + the loss + target critic k's soft update (critic k is final by then; the actor's loss does not
+//             read the target)
+//  10-16      as DADDPG's 10-16 with critic k in the critic's place; 16 soft-updates target actor k
+// The other critic is read (darc) and never written; DATD3 has no fifth problem and takes its target from T itself.
 #include <cmath>
 
 #include "armenv_engine.h"
@@ -159,7 +174,7 @@ void adam_tensors(AdamArgs &P, const ArmEnvMlpRW &p, const ArmEnvMlpRW &m, const
   }
 }
 
-// Args: ArmEnvTd3Args or ArmEnvDaddpgArgs (beta1, beta2, eps, tau)
+// Args: ArmEnvTd3Args, ArmEnvDaddpgArgs or ArmEnvDatd3Args (beta1, beta2, eps, tau)
 template <class Args>
 int launch_adam(AdamArgs &P, float lr, int64_t step, const Args *a, hipStream_t s) {
   P.beta1 = a->beta1; P.beta2 = a->beta2; P.eps = a->eps; P.tau = a->tau;
@@ -178,7 +193,7 @@ bool mlp_aligned(const ArmEnvMlpRW &m) { return al16(m.W1) && al16(m.b1) && al16
 
 constexpr int64_t kMaxBatch = (int64_t)1 << 20;
 
-// Argument checks both updates share (Args: ArmEnvTd3Args or ArmEnvDaddpgArgs); each names the field it refuses.
+// Argument checks the updates share (Args: ArmEnvTd3Args, ArmEnvDaddpgArgs or ArmEnvDatd3Args); each names the field it refuses.
 template <class Args>
 int check_sizes(const char *fn, const Args *a) {
   if (!a) return fail(ARMENV_EINVAL, "%s: args is NULL", fn);
@@ -246,6 +261,22 @@ WsD daddpg_layout(int64_t B) {
   const int64_t part = take(w.S * w.split_stride);
   w.pW3 += part; w.pW2 += part; w.pW1 += part;
   w.pa3 += part; w.pa2 += part; w.pa1 += part;
+  w.total = o;
+  return w;
+}
+
+// DATD3 / DARC: DADDPG's layout (the same activations, deltas and actor-sized partial slices, for ONE stepped critic) followed by the
+// other critic's two hidden layers and a two-column loss block, both written only when `darc`
+struct WsT : WsD {
+  int64_t oh1, oh2, loss2;
+};
+
+WsT datd3_layout(int64_t B) {
+  WsT w{};
+  static_cast<WsD &>(w) = daddpg_layout(B);
+  int64_t o = w.total;
+  auto take = [&](int64_t n) { const int64_t r = o; o += up64(n); return r; };
+  w.oh1 = take(B * LRN_H); w.oh2 = take(B * LRN_H); w.loss2 = take(2 * B);
   w.total = o;
   return w;
 }
@@ -345,7 +376,7 @@ int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
     for (int i = 0; i < 2; ++i)
       adam_tensors(P, *Q[i], i ? a->q2_m : a->q1_m, i ? a->q2_v : a->q1_v, *TQ[i], K1, 1, ws + w.pW1[i], ws + w.pW2[i], ws + w.pW3[i]);
     P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = a->with_actor;
-    P.loss_rows = ws + w.loss_rows; P.loss_cols = 2; P.B = B; P.inv_b = 1.0f / (float)B; P.loss = a->loss_dev;
+    P.loss_rows = ws + w.loss_rows; P.loss_cols = 2; P.loss_w1 = 1.0f; P.B = B; P.inv_b = 1.0f / (float)B; P.loss = a->loss_dev;
     LRN_TRY(launch_adam(P, a->critic_lr, a->critic_step, a, s));
   }
   if (!a->with_actor) return ARMENV_OK;
@@ -470,6 +501,147 @@ int armenv_daddpg_update(const ArmEnvDaddpgArgs *a, void *stream) {
   }
 
   // 10-12: critic(s, actor_k(s)) with the stepped critic and its backward to the critic's input; c1 / dc2 / dc1 / da2 / da1 reuse
+  // the target path's buffers
+  float *c1 = ws + w.ta1[0], *dc2 = ws + w.ta2[0], *dc1 = ws + w.tq1[0], *da2 = ws + w.tq1[1], *da1 = ws + w.tq2[0];
+  L.forward(feat2(a->states_dev, D, ws + w.api, LRN_A, K1, B), K1, Q.W1, Q.b1, c1, B);
+  LRN_TRY(L.launch(s));
+  L.forward(feat(c1, H, H, B), H, Q.W2, Q.b2, dc2, B, EPI_DRELU_W, Q.W3, -1.0f / (float)B);
+  LRN_TRY(L.launch(s));
+  L.backward(dc2, Q.W2, c1, dc1, B);
+  LRN_TRY(L.launch(s));
+
+  // 13: through cat -> tanh -> actor k's fc3
+  ActorBackArgs ab{};
+  ab.B = B; ab.in_dim = K1; ab.state_dim = D; ab.bound = a->action_bound; ab.dc1 = dc1; ab.Wq1 = Q.W1;
+  ab.tanh_a = ws + w.tanh_a; ab.h2 = ws + w.ah2; ab.W3 = act.W3; ab.du = ws + w.du; ab.da2 = da2;
+  hipLaunchKernelGGL(actor_back_kernel, dim3(row_blocks), dim3(256), 0, s, ab);
+  HIP_TRY(hipGetLastError());
+
+  // 14-15: actor k's backward and weight-gradient partials (the critic's partials are consumed: same slices)
+  L.backward(da2, act.W2, ws + w.ah1, da1, B);
+  L.wgrad(ws + w.du, LRN_A, feat(ws + w.ah2, H, H, B, 1), H, ws + w.pa3, H + 1, B, w.split_stride);
+  L.wgrad(da2, H, feat(ws + w.ah1, H, H, B, 1), H, ws + w.pa2, H + 1, B, w.split_stride);
+  LRN_TRY(L.launch(s));
+  L.wgrad(da1, H, feat(a->states_dev, D, D, B, 1), D, ws + w.pa1, kW1Ld, B, w.split_stride);
+  LRN_TRY(L.launch(s));
+
+  // 16: actor k's Adam + its target's soft update
+  AdamArgs P{};
+  adam_tensors(P, act, second ? a->actor2_m : a->actor1_m, second ? a->actor2_v : a->actor1_v, t_act, D, LRN_A, ws + w.pa1, ws + w.pa2,
+               ws + w.pa3);
+  P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = 1;
+  return launch_adam(P, a->actor_lr, a->actor_step, a, s);
+}
+
+int64_t armenv_datd3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch) {
+  if (state_dim < 1 || state_dim > 12 || hidden_dim != LRN_H || batch < 1 || batch > kMaxBatch) return -1;
+  return datd3_layout(batch).total * (int64_t)sizeof(float);
+}
+
+int armenv_datd3_update(const ArmEnvDatd3Args *a, void *stream) {
+  static const char *fn = "armenv_datd3_update";
+  LRN_TRY(check_sizes(fn, a));
+  if (a->update_actor != 1 && a->update_actor != 2) return fail(ARMENV_EINVAL, "%s: update_actor %d must be 1 or 2", fn, a->update_actor);
+  if (a->darc != 0 && a->darc != 1) return fail(ARMENV_EINVAL, "%s: darc %d must be 0 or 1", fn, a->darc);
+  if (a->critic_step < 1) return fail(ARMENV_EINVAL, "%s: critic_step must be >= 1", fn);
+  if (a->actor_step < 1) return fail(ARMENV_EINVAL, "%s: actor_step must be >= 1", fn);
+  const bool darc = a->darc == 1;
+  // q_weight and regularization_weight are read only when darc
+  const NamedF hp[] = {
+      {"action_bound", a->action_bound, a->action_bound > 0.f}, {"gamma", a->gamma, a->gamma >= 0.f && a->gamma <= 1.f},
+      {"tau", a->tau, a->tau >= 0.f && a->tau <= 1.f}, {"policy_noise", a->policy_noise, a->policy_noise >= 0.f},
+      {"noise_clip", a->noise_clip, a->noise_clip >= 0.f}, {"actor_lr", a->actor_lr, a->actor_lr >= 0.f},
+      {"critic_lr", a->critic_lr, a->critic_lr >= 0.f}, {"beta1", a->beta1, a->beta1 >= 0.f && a->beta1 < 1.f},
+      {"beta2", a->beta2, a->beta2 >= 0.f && a->beta2 < 1.f}, {"eps", a->eps, a->eps > 0.f},
+      {"q_weight", darc ? a->q_weight : 0.f, !darc || (a->q_weight >= 0.f && a->q_weight <= 1.f)},
+      {"regularization_weight", darc ? a->regularization_weight : 0.f, !darc || a->regularization_weight >= 0.f}};
+  const NamedNet nets[] = {
+      {"actor1", &a->actor1}, {"actor2", &a->actor2}, {"critic1", &a->critic1}, {"critic2", &a->critic2},
+      {"target_actor1", &a->target_actor1}, {"target_actor2", &a->target_actor2}, {"target_critic1", &a->target_critic1},
+      {"target_critic2", &a->target_critic2}, {"actor1_m", &a->actor1_m}, {"actor1_v", &a->actor1_v}, {"actor2_m", &a->actor2_m},
+      {"actor2_v", &a->actor2_v}, {"critic1_m", &a->critic1_m}, {"critic1_v", &a->critic1_v}, {"critic2_m", &a->critic2_m},
+      {"critic2_v", &a->critic2_v}};
+  LRN_TRY(check_buffers(fn, a, hp, nets, armenv_datd3_workspace_bytes(a->state_dim, a->hidden_dim, a->batch),
+                        "armenv_datd3_workspace_bytes"));
+
+  DeviceGuard guard_(a->device);
+  if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int D = a->state_dim, K1 = D + LRN_A, H = LRN_H;
+  const int64_t B = a->batch;
+  const WsT w = datd3_layout(B);
+  float *ws = static_cast<float *>(a->workspace_dev);
+  const bool second = a->update_actor == 2;
+  const ArmEnvMlpRW &Q = second ? a->critic2 : a->critic1, &TQk = second ? a->target_critic2 : a->target_critic1;
+  const ArmEnvMlpRW &Qo = second ? a->critic1 : a->critic2;     // read only (darc)
+  const ArmEnvMlpRW &act = second ? a->actor2 : a->actor1, &t_act = second ? a->target_actor2 : a->target_actor1;
+  const ArmEnvMlpRW *TA[2] = {&a->target_actor1, &a->target_actor2}, *TQ[2] = {&a->target_critic1, &a->target_critic2};
+  const Feat s2_only = feat(a->next_states_dev, D, D, B);
+  const Feat sa = feat2(a->states_dev, D, a->actions_dev, LRN_A, K1, B);
+  Launcher L;
+
+  // 1-2: layers 1 and 2 of both target actors, critic k, actor k and (darc) the other critic
+  for (int i = 0; i < 2; ++i) L.forward(s2_only, D, TA[i]->W1, TA[i]->b1, ws + w.ta1[i], B);
+  L.forward(sa, K1, Q.W1, Q.b1, ws + w.h1, B);
+  L.forward(feat(a->states_dev, D, D, B), D, act.W1, act.b1, ws + w.ah1, B);
+  if (darc) L.forward(sa, K1, Qo.W1, Qo.b1, ws + w.oh1, B);
+  LRN_TRY(L.launch(s));
+  for (int i = 0; i < 2; ++i) L.forward(feat(ws + w.ta1[i], H, H, B), H, TA[i]->W2, TA[i]->b2, ws + w.ta2[i], B);
+  L.forward(feat(ws + w.h1, H, H, B), H, Q.W2, Q.b2, ws + w.h2, B);
+  L.forward(feat(ws + w.ah1, H, H, B), H, act.W2, act.b2, ws + w.ah2, B);
+  if (darc) L.forward(feat(ws + w.oh1, H, H, B), H, Qo.W2, Qo.b2, ws + w.oh2, B);
+  LRN_TRY(L.launch(s));
+
+  // 3: both noisy clamped proposals and actor k's action
+  Datd3ActorHeadArgs ah{};
+  ah.B = B; ah.bound = a->action_bound; ah.policy_noise = a->policy_noise; ah.noise_clip = a->noise_clip;
+  ah.noise = a->noise_dev; ah.seed = a->seed; ah.draw = a->draw;
+  for (int i = 0; i < 2; ++i) { ah.t_h2[i] = ws + w.ta2[i]; ah.t_W3[i] = TA[i]->W3; ah.t_b3[i] = TA[i]->b3; ah.a2[i] = ws + w.a2[i]; }
+  ah.h2 = ws + w.ah2; ah.W3 = act.W3; ah.b3 = act.b3; ah.a = ws + w.api; ah.tanh_out = ws + w.tanh_a;
+  const unsigned row_blocks = grid_for(B, 4);
+  hipLaunchKernelGGL(datd3_actor_head_kernel, dim3(row_blocks * 2u), dim3(256), 0, s, ah);
+  HIP_TRY(hipGetLastError());
+
+  // 4-5: target critic j over its own actor's proposal
+  for (int i = 0; i < 2; ++i) L.forward(feat2(a->next_states_dev, D, ws + w.a2[i], LRN_A, K1, B), K1, TQ[i]->W1, TQ[i]->b1, ws + w.tq1[i], B);
+  LRN_TRY(L.launch(s));
+  for (int i = 0; i < 2; ++i) L.forward(feat(ws + w.tq1[i], H, H, B), H, TQ[i]->W2, TQ[i]->b2, ws + w.tq2[i], B);
+  LRN_TRY(L.launch(s));
+
+  // 6: target, loss rows, critic k's deltas
+  float *loss_rows = ws + (darc ? w.loss2 : w.loss_rows);
+  Datd3CriticHeadArgs ch{};
+  ch.B = B; ch.gamma = a->gamma; ch.inv_b = 1.0f / (float)B; ch.rewards = a->rewards_dev; ch.dones = a->dones_dev;
+  ch.darc = a->darc;
+  if (darc) {
+    ch.w_min = a->q_weight; ch.w_max = (float)(1.0 - (double)a->q_weight); ch.reg = a->regularization_weight;
+    ch.o_h2 = ws + w.oh2; ch.o_W3 = Qo.W3; ch.o_b3 = Qo.b3;
+  }
+  for (int i = 0; i < 2; ++i) { ch.t_h2[i] = ws + w.tq2[i]; ch.t_W3[i] = TQ[i]->W3; ch.t_b3[i] = TQ[i]->b3; }
+  ch.h2 = ws + w.h2; ch.W3 = Q.W3; ch.b3 = Q.b3; ch.d3 = ws + w.d3; ch.d2 = ws + w.d2; ch.loss_rows = loss_rows;
+  hipLaunchKernelGGL(datd3_critic_head_kernel, dim3(row_blocks), dim3(256), 0, s, ch);
+  HIP_TRY(hipGetLastError());
+
+  // 7-8: critic k's backward and weight-gradient partials
+  L.backward(ws + w.d2, Q.W2, ws + w.h1, ws + w.d1, B);
+  L.wgrad(ws + w.d3, 1, feat(ws + w.h2, H, H, B, 1), H, ws + w.pW3, H + 1, B, w.split_stride);
+  L.wgrad(ws + w.d2, H, feat(ws + w.h1, H, H, B, 1), H, ws + w.pW2, H + 1, B, w.split_stride);
+  LRN_TRY(L.launch(s));
+  L.wgrad(ws + w.d1, H, feat2(a->states_dev, D, a->actions_dev, LRN_A, K1, B, 1), K1, ws + w.pW1, kW1Ld, B, w.split_stride);
+  LRN_TRY(L.launch(s));
+
+  // 9: critic k's Adam + the loss + target critic k's soft update
+  {
+    AdamArgs P{};
+    adam_tensors(P, Q, second ? a->critic2_m : a->critic1_m, second ? a->critic2_v : a->critic1_v, TQk, K1, 1, ws + w.pW1, ws + w.pW2,
+                 ws + w.pW3);
+    P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = 1;
+    P.loss_rows = loss_rows; P.loss_cols = darc ? 2 : 1; P.loss_w1 = darc ? a->regularization_weight : 0.f;
+    P.B = B; P.inv_b = 1.0f / (float)B; P.loss = a->loss_dev;
+    LRN_TRY(launch_adam(P, a->critic_lr, a->critic_step, a, s));
+  }
+
+  // 10-12: critic_k(s, actor_k(s)) with the stepped critic and its backward to the critic's input; c1 / dc2 / dc1 / da2 / da1 reuse
   // the target path's buffers
   float *c1 = ws + w.ta1[0], *dc2 = ws + w.ta2[0], *dc1 = ws + w.tq1[0], *da2 = ws + w.tq1[1], *da1 = ws + w.tq2[0];
   L.forward(feat2(a->states_dev, D, ws + w.api, LRN_A, K1, B), K1, Q.W1, Q.b1, c1, B);

@@ -36,6 +36,8 @@ extern "C" {
 
 #define ARMENV_NJ 7
 #define ARMENV_ABI_VERSION 8   /* 8: + armenv_daddpg_update, armenv_daddpg_workspace_bytes, ArmEnvDaddpgArgs;
+                                     still 8: + armenv_datd3_update, armenv_datd3_workspace_bytes, ArmEnvDatd3Args -- purely additive
+                                     (two functions, one struct, nothing existing moves), so the number did not change;
                                   7: + armenv_td3_update, armenv_td3_workspace_bytes, ArmEnvMlpRW, ArmEnvTd3Args;
                                   6: + armenv_set_policy_daddpg, armenv_episode_returns_f32, ARMENV_POLICY_DADDPG; ArmEnvConfig unchanged since 5 */
 
@@ -513,6 +515,51 @@ typedef struct ArmEnvDaddpgArgs {
 /* Bytes of workspace armenv_daddpg_update needs for (state_dim, hidden_dim, batch); -1 for unsupported sizes. */
 int64_t armenv_daddpg_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch);
 int armenv_daddpg_update(const ArmEnvDaddpgArgs *args, void *stream);
+
+/* ---- fused DATD3 / DARC learner: ONE update of DATD3_MLP (the reference's algo/DATD3/DATD3_mlp.py:146-211) or, with `darc`, of
+ * DARC_MLP (algo/DARC/DARC_mlp.py:140-222), over two actors (fc1-3, tanh x action_bound) and two critics over cat(s, a) (fc1-3 each),
+ * hidden_dim 256.  The reference's train() is two updates on the same batch: update_actor = 1, then 2.  With k = update_actor:
+ *   noise  = clamp(N(0,1) policy_noise, +-noise_clip), ONE draw per row shared by both proposals
+ *   a2_j   = clamp(target_actor_j(s2) + noise, +-action_bound), j = 1, 2
+ *   T      = min(target_critic1(s2, a2_1), target_critic2(s2, a2_2))
+ *   target = r + (1 - d) gamma T                                      (darc: T replaced by q_weight T + (1 - q_weight) T, two
+ *                                                                      rounded products and a rounded sum, as the reference's)
+ *   critic k: loss = mse(critic_k(s, a), target)  (darc: + regularization_weight mse(critic_k(s, a), critic_other(s, a))), one
+ *   Adam step on critic k ONLY; actor k: loss -mean(critic_k(s, actor_k(s))) with critic k AFTER its step, one Adam step on actor k;
+ *   then the Polyak soft updates (tau) of target_actor_k and target_critic_k.
+ * Adam is torch.optim.Adam's: no weight decay, bias corrections 1 - beta^step from the 1-based step numbers passed in; four
+ * optimisers (critic 1, critic 2, actor 1, actor 2), each with its own step counter.  Parameters, targets and moments are updated in
+ * place; the other actor, the other critic, their targets and their moments are not touched.  The noise is Philox4x32-10 keyed by
+ * (seed, row, draw), Box-Muller in f32; noise_dev (nullable, [B][action_dim] standard normals) replaces it.
+ *
+ * Properties (as armenv_td3_update): every contraction runs on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32); batch sums are
+ * per-slice partials added in slice order (no atomics), so an update is bitwise reproducible run to run.  The call only enqueues
+ * kernels on `stream`: 16 launches; no allocation, no memset, no host synchronisation, so it can be captured into a graph.  All
+ * intermediates live in the caller's workspace (armenv_datd3_workspace_bytes).  Every argument is validated before any HIP call:
+ * a bad one returns ARMENV_EINVAL and armenv_last_error() names the field. */
+typedef struct ArmEnvDatd3Args {
+  int32_t device, state_dim, action_dim, hidden_dim;   /* state_dim 1..12 (6 reach, 9 push / pick), action_dim 3, hidden_dim 256 */
+  int64_t batch;                                       /* B >= 1, any size up to 2^20 */
+  float action_bound, gamma, tau, policy_noise, noise_clip, actor_lr, critic_lr, beta1, beta2, eps;
+  float q_weight, regularization_weight;               /* read only when darc: q_weight in [0, 1], regularization_weight >= 0 */
+  int64_t critic_step;                                 /* 1-based Adam step number of THIS update: critic k's optimiser */
+  int64_t actor_step;                                  /* ... and actor k's */
+  int32_t update_actor;                                /* k: 1 or 2 */
+  int32_t darc;                                        /* 0: DATD3, 1: DARC */
+  uint64_t seed, draw;
+  const float *noise_dev;                              /* nullable [B][action_dim] standard normals */
+  ArmEnvMlpRW actor1, actor2, critic1, critic2, target_actor1, target_actor2, target_critic1, target_critic2;
+  ArmEnvMlpRW actor1_m, actor1_v, actor2_m, actor2_v, critic1_m, critic1_v, critic2_m, critic2_v;   /* Adam moments, same shapes */
+  const float *states_dev, *actions_dev, *next_states_dev, *rewards_dev;   /* [B][state_dim], [B][3], [B][state_dim], [B] */
+  const uint8_t *dones_dev;                            /* [B] */
+  float *loss_dev;                                     /* nullable out: f32 scalar, critic k's full loss (darc: regulariser included) */
+  void *workspace_dev;                                 /* device, 16-byte aligned */
+  int64_t workspace_bytes;
+} ArmEnvDatd3Args;
+
+/* Bytes of workspace armenv_datd3_update needs for (state_dim, hidden_dim, batch), darc or not; -1 for unsupported sizes. */
+int64_t armenv_datd3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch);
+int armenv_datd3_update(const ArmEnvDatd3Args *args, void *stream);
 
 /* Measurement aid (bench.py's roofline.valu.one_wave_per_simd; no reference counterpart): the interval at which SIMDs issue
  * independent 64-lane v_fma_f64 (precision 64) / v_fma_f32 (32) instructions when every SIMD of `device` holds
