@@ -6,31 +6,29 @@ run, no hipGraph needed.  ``train`` is the reference's: update k = 1, then updat
 The networks are the same torch modules as armenv.datd3.DATD3's, created in the same order (so ``torch.manual_seed(s)`` gives both
 learners the same initial weights) and updated in place by the kernels; the Adam moments are tensors of this object and the four
 Adam step counters live on the host."""
-import ctypes as C
-
 import torch
 
 from . import _lib as L
-from .fused_td3 import _mlp, _mlp_of
+from .fused_base import FusedLearner, _mlp, _mlp_of
 from .policies import QValueNet
 from .td3 import Actor
 
 _LEARNING = ("actor1", "actor2", "critic1", "critic2")
 
 
-class FusedDATD3:
+class FusedDATD3(FusedLearner):
     """armenv.datd3.DATD3's constructor and public surface (``train(batch, noise=None)``, ``update``, ``total_it``, the eight modules,
     the ``actor`` property, ``take_action``, ``policy_state_dicts()``, ``_nets()``) with the update in HIP; ``load_from`` copies a
     DATD3's whole state.  ``seed`` keys the in-kernel target-policy noise (Philox4x32-10 over (seed, row, update number): both
     proposals of a row receive the same noise); ``noise=`` supplies it instead."""
 
     _darc = 0
+    _fn, _Args = "datd3", L.ArmEnvDatd3Args
+    _hyper = ("policy_noise", "noise_clip", "seed", "q_weight", "regularization_weight")
 
     def __init__(self, state_dim, action_dim, action_bound, hidden_dim=256, actor_lr=1e-3, critic_lr=1e-3, tau=0.005, gamma=0.98,
                  policy_noise=0.2, noise_clip=0.5, policy_freq=3, device="cuda:0", seed=0):
-        name = type(self).__name__
-        if hidden_dim != 256 or action_dim != 3 or not 1 <= state_dim <= 12:
-            raise ValueError("%s: the fused update is built for hidden_dim 256, action_dim 3, state_dim 1..12" % name)
+        self._check_shapes(state_dim, action_dim, hidden_dim)
         self.device = torch.device(device)
         mk_a = lambda: Actor(state_dim, hidden_dim, action_dim, action_bound).to(self.device)
         mk_q = lambda: QValueNet(state_dim, hidden_dim, action_dim).to(self.device)
@@ -68,14 +66,8 @@ class FusedDATD3:
 
     def _static_args(self):
         """the part of ArmEnvDatd3Args that does not change between updates"""
-        a = L.ArmEnvDatd3Args()
-        a.device = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        a.state_dim, a.action_dim, a.hidden_dim = self.state_dim, self.action_dim, self.hidden_dim
-        a.action_bound, a.gamma, a.tau = self.action_bound, self.gamma, self.tau
-        a.policy_noise, a.noise_clip, a.actor_lr, a.critic_lr = self.policy_noise, self.noise_clip, self.actor_lr, self.critic_lr
-        a.beta1, a.beta2, a.eps = self.betas[0], self.betas[1], self.eps
-        a.darc, a.q_weight, a.regularization_weight = self._darc, self.q_weight, self.regularization_weight
-        a.seed = self.seed
+        a = super()._static_args()
+        a.darc = self._darc
         for name in _LEARNING:
             setattr(a, name, _mlp(getattr(self, name)))
             setattr(a, "target_" + name, _mlp(getattr(self, "target_" + name)))
@@ -83,55 +75,14 @@ class FusedDATD3:
             setattr(a, name + "_v", _mlp_of(getattr(self, name + "_v")))
         return a
 
-    def batch_buffers(self, batch_size):
-        """static input tensors of `batch_size` rows that ``TrajectoryStore.sample(out=...)`` fills in place"""
-        B, D, dev = int(batch_size), self.state_dim, self.device
-        return dict(states=torch.zeros(B, D, device=dev), actions=torch.zeros(B, self.action_dim, device=dev),
-                    next_states=torch.zeros(B, D, device=dev), rewards=torch.zeros(B, device=dev),
-                    dones=torch.zeros(B, dtype=torch.uint8, device=dev))
-
-    def _workspace(self, B):
-        n = L.load().armenv_datd3_workspace_bytes(self.state_dim, self.hidden_dim, B)
-        if n < 0:
-            raise ValueError("%s: unsupported batch size %d" % (type(self).__name__, B))
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._ws
-
-    def _inputs(self, batch):
-        dev = self.device
-        f32 = lambda k: batch[k].to(dev, torch.float32).contiguous()
-        r = batch["rewards"].to(dev, torch.float32).reshape(-1).contiguous()
-        d = batch["dones"].to(dev)
-        d = (d if d.dtype == torch.uint8 else (d != 0).to(torch.uint8)).reshape(-1).contiguous()
-        return f32("states"), f32("actions"), r, f32("next_states"), d
-
     def _update(self, s, a, r, s2, d, update_a1, noise=None):
         """one armenv_datd3_update over prepared tensors; its `draw` is the update's number"""
-        dev, B = self.device, s.shape[0]
         self.total_it += 1
-        if self._args is None:
-            self._args = self._static_args()
-        args = self._args
-        ws = self._workspace(B)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        if noise is not None:
-            noise = noise.to(dev, torch.float32).contiguous()
-            if tuple(noise.shape) != (B, self.action_dim):
-                raise ValueError("noise must be [B][%d] standard normals" % self.action_dim)
         k = 1 if update_a1 else 2
-        args.batch = B
-        args.update_actor = k
-        args.critic_step = getattr(self, "critic%d_step" % k) + 1
-        args.actor_step = getattr(self, "actor%d_step" % k) + 1
-        args.draw = self.total_it
-        args.noise_dev = noise.data_ptr() if noise is not None else None
-        args.states_dev, args.actions_dev, args.next_states_dev = s.data_ptr(), a.data_ptr(), s2.data_ptr()
-        args.rewards_dev, args.dones_dev, args.loss_dev = r.data_ptr(), d.data_ptr(), loss.data_ptr()
-        args.workspace_dev, args.workspace_bytes = ws.data_ptr(), ws.numel()
-        L.check(L.load().armenv_datd3_update(C.byref(args), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        setattr(self, "critic%d_step" % k, args.critic_step)
-        setattr(self, "actor%d_step" % k, args.actor_step)
+        steps = dict(critic_step=getattr(self, "critic%d_step" % k) + 1, actor_step=getattr(self, "actor%d_step" % k) + 1)
+        loss = self._call(s, a, r, s2, d, self._noise(noise, s.shape[0]), update_actor=k, draw=self.total_it, **steps)
+        setattr(self, "critic%d_step" % k, steps["critic_step"])
+        setattr(self, "actor%d_step" % k, steps["actor_step"])
         return loss
 
     def update(self, batch, update_a1=True, noise=None):
@@ -146,36 +97,14 @@ class FusedDATD3:
         n1, n2 = (None, None) if noise is None else noise
         return self._update(*inputs, True, n1), self._update(*inputs, False, n2)
 
-    @torch.no_grad()
     def load_from(self, learner):
         """Copies parameters, Adam moments, the four step counters and total_it from an armenv.datd3.DATD3 / DARC (identical state for
         comparisons)."""
-        for mine, theirs in zip(self._nets(), learner._nets()):
-            for p, q in zip(mine.parameters(), theirs.parameters()):
-                p.copy_(q)
-        for name in _LEARNING:
-            opt = getattr(learner, name + "_opt")
-            step = 0
-            for p, m, v in zip(getattr(learner, name).parameters(), getattr(self, name + "_m"), getattr(self, name + "_v")):
-                st = opt.state.get(p, {})
-                if "exp_avg" in st:
-                    m.copy_(st["exp_avg"])
-                    v.copy_(st["exp_avg_sq"])
-                    step = int(st["step"])
-                else:
-                    m.zero_()
-                    v.zero_()
-            setattr(self, name + "_step", step)
-        self.total_it = learner.total_it
+        self._load_from(learner, _LEARNING)
 
-    @torch.no_grad()
     def take_action(self, state):
         """DATD3_MLP.take_action (DATD3_mlp.py:88-109), as armenv.datd3.DATD3.take_action"""
-        import numpy as np
-        s = torch.tensor(np.asarray([state], dtype=np.float32), device=self.device)
-        a1, a2 = self.actor1(s), self.actor2(s)
-        q1, q2 = self.critic1(s, a1), self.critic2(s, a2)
-        return (a1 if bool(q1 >= q2) else a2).cpu().numpy()[0]
+        return self._take_action_of_two(state, self.critic1, self.critic2)
 
     def policy_state_dicts(self):
         """(actor1, actor2, critic1, critic2) for BatchedArmEnv.set_policy_datd3 / set_policy_darc"""

@@ -178,6 +178,66 @@ AE_DEV void box_muller(uint32_t w0, uint32_t w1, float &z0, float &z1) {
   z1 = r * sn;
 }
 
+// The per-row pieces of the head kernels, each written once.  The build has -ffp-contract=off, so a kernel built from them performs
+// the IEEE operations it would perform written out, in the same order.
+
+// the 256 -> 3 head of row b: u[j] = h2[b] . W3[j] + b3[j], the same value in every lane
+AE_DEV void head3(const float *h2, const float *W3, const float *b3, int64_t b, int lane, float (&u)[LRN_A]) {
+  const float4 h = row4(h2, b, lane);
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) u[j] = wave_sum(dot4(h, row4(W3, j, lane))) + b3[j];
+}
+
+// the 256 -> 1 head of a row from its lane's four hidden units h and weights w: h2[b] . W3[0] + b3[0]
+AE_DEV float head1(float4 h, float4 w, const float *b3) { return wave_sum(dot4(h, w)) + b3[0]; }
+AE_DEV float head1(const float *h2, const float *W3, const float *b3, int64_t b, int lane) {
+  return head1(row4(h2, b, lane), row4(W3, 0, lane), b3);
+}
+
+// row b's target-policy noise clamp(z policy_noise, +-noise_clip): z from `noise` [B][3] when given, else drawn by Philox4x32-10
+// keyed by seed, counter (row, draw) -- independent of launch geometry -- and Box-Muller
+AE_DEV void row_noise(const float *noise, uint64_t seed, uint64_t draw, float policy_noise, float noise_clip, int64_t b,
+                      float (&nz)[LRN_A]) {
+  float z[4];
+  if (noise) {
+#pragma unroll
+    for (int j = 0; j < LRN_A; ++j) z[j] = noise[b * LRN_A + j];
+  } else {
+    uint32_t c[4] = {(uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)draw, (uint32_t)(draw >> 32)};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    box_muller(c[0], c[1], z[0], z[1]);
+    box_muller(c[2], c[3], z[2], z[3]);
+  }
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) nz[j] = fminf(fmaxf(z[j] * policy_noise, -noise_clip), noise_clip);
+}
+
+// the noisy clamped proposal clamp(bound tanh(u) + nz, +-bound)
+AE_DEV float proposal(float u, float nz, float bound) {
+  const float v = tanhf(u) * bound + nz;
+  return fminf(fmaxf(v, -bound), bound);
+}
+
+// a = bound tanh(u) of row b, and tanh itself when `keep_tanh` (the backward pass reads it)
+AE_DEV void store_action(const float (&u)[LRN_A], float bound, float *a, float *tanh_out, bool keep_tanh, int64_t b) {
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) {
+    const float th = tanhf(u[j]);
+    if (keep_tanh) tanh_out[b * LRN_A + j] = th;
+    a[b * LRN_A + j] = th * bound;
+  }
+}
+
+// d2[b] = (d3 W3) relu'(h2[b]): the lane's four hidden units h and weights w
+AE_DEV void store_d2(float4 h, float4 w, float d3, float *d2, int64_t b, int lane) {
+  float4 d;
+  d.x = h.x > 0.f ? d3 * w.x : 0.f;
+  d.y = h.y > 0.f ? d3 * w.y : 0.f;
+  d.z = h.z > 0.f ? d3 * w.z : 0.f;
+  d.w = h.w > 0.f ? d3 * w.w : 0.f;
+  reinterpret_cast<float4 *>(d2 + b * LRN_H)[lane] = d;
+}
+
 struct ActorHeadArgs {
   int64_t B;
   // target rows: a2 = clamp(bound tanh(h2 W3^T + b3) + clamp(noise policy_noise, +-noise_clip), +-bound)
@@ -198,38 +258,17 @@ __global__ __launch_bounds__(256) void actor_head_kernel(ActorHeadArgs P) {
   const bool actor = (int64_t)blockIdx.x >= nb;
   const int64_t b = ((int64_t)blockIdx.x - (actor ? nb : 0)) * 4 + (threadIdx.x >> 6);
   if (b >= P.B) return;
-  const float *h2 = actor ? P.h2 : P.t_h2, *W3 = actor ? P.W3 : P.t_W3, *b3 = actor ? P.b3 : P.t_b3;
-  const float4 h = row4(h2, b, lane);
   float u[LRN_A];
-#pragma unroll
-  for (int j = 0; j < LRN_A; ++j) u[j] = wave_sum(dot4(h, row4(W3, j, lane))) + b3[j];
+  head3(actor ? P.h2 : P.t_h2, actor ? P.W3 : P.t_W3, actor ? P.b3 : P.t_b3, b, lane, u);
   if (lane != 0) return;
   if (actor) {
-#pragma unroll
-    for (int j = 0; j < LRN_A; ++j) {
-      const float th = tanhf(u[j]);
-      P.tanh_out[b * LRN_A + j] = th;
-      P.a[b * LRN_A + j] = th * P.bound;
-    }
+    store_action(u, P.bound, P.a, P.tanh_out, true, b);
     return;
   }
-  float z[4];
-  if (P.noise) {
+  float nz[LRN_A];
+  row_noise(P.noise, P.seed, P.draw, P.policy_noise, P.noise_clip, b, nz);
 #pragma unroll
-    for (int j = 0; j < LRN_A; ++j) z[j] = P.noise[b * LRN_A + j];
-  } else {
-    // Philox4x32-10 keyed by seed, counter (row, draw): independent of launch geometry
-    uint32_t c[4] = {(uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)P.draw, (uint32_t)(P.draw >> 32)};
-    philox4x32_10(c, (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
-    box_muller(c[0], c[1], z[0], z[1]);
-    box_muller(c[2], c[3], z[2], z[3]);
-  }
-#pragma unroll
-  for (int j = 0; j < LRN_A; ++j) {
-    const float nz = fminf(fmaxf(z[j] * P.policy_noise, -P.noise_clip), P.noise_clip);
-    const float v = tanhf(u[j]) * P.bound + nz;
-    P.a2[b * LRN_A + j] = fminf(fmaxf(v, -P.bound), P.bound);
-  }
+  for (int j = 0; j < LRN_A; ++j) P.a2[b * LRN_A + j] = proposal(u[j], nz[j], P.bound);
 }
 
 struct CriticHeadArgs {
@@ -252,8 +291,8 @@ __global__ __launch_bounds__(256) void critic_head_kernel(CriticHeadArgs P) {
   float tq[2], q[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    tq[i] = wave_sum(dot4(row4(P.t_h2[i], b, lane), row4(P.t_W3[i], 0, lane))) + P.t_b3[i][0];
-    q[i] = wave_sum(dot4(row4(P.h2[i], b, lane), row4(P.W3[i], 0, lane))) + P.b3[i][0];
+    tq[i] = head1(P.t_h2[i], P.t_W3[i], P.t_b3[i], b, lane);
+    q[i] = head1(P.h2[i], P.W3[i], P.b3[i], b, lane);
   }
   const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
   const float target = P.rewards[b] + notdone * P.gamma * fminf(tq[0], tq[1]);
@@ -265,13 +304,7 @@ __global__ __launch_bounds__(256) void critic_head_kernel(CriticHeadArgs P) {
       P.d3[i][b] = d3;
       P.loss_rows[2 * b + i] = e * e;
     }
-    const float4 h = row4(P.h2[i], b, lane), w = row4(P.W3[i], 0, lane);
-    float4 d;
-    d.x = h.x > 0.f ? d3 * w.x : 0.f;
-    d.y = h.y > 0.f ? d3 * w.y : 0.f;
-    d.z = h.z > 0.f ? d3 * w.z : 0.f;
-    d.w = h.w > 0.f ? d3 * w.w : 0.f;
-    reinterpret_cast<float4 *>(P.d2[i] + b * LRN_H)[lane] = d;
+    store_d2(row4(P.h2[i], b, lane), row4(P.W3[i], 0, lane), d3, P.d2[i], b, lane);
   }
 }
 
@@ -291,17 +324,10 @@ __global__ __launch_bounds__(256) void daddpg_actor_head_kernel(DaddpgActorHeadA
   const int k = (int)((int64_t)blockIdx.x / nb);
   const int64_t b = ((int64_t)blockIdx.x - k * nb) * 4 + (threadIdx.x >> 6);
   if (k > 2 || b >= P.B) return;
-  const float4 h = row4(P.h2[k], b, lane);
   float u[LRN_A];
-#pragma unroll
-  for (int j = 0; j < LRN_A; ++j) u[j] = wave_sum(dot4(h, row4(P.W3[k], j, lane))) + P.b3[k][j];
+  head3(P.h2[k], P.W3[k], P.b3[k], b, lane, u);
   if (lane != 0) return;
-#pragma unroll
-  for (int j = 0; j < LRN_A; ++j) {
-    const float th = tanhf(u[j]);
-    if (k == 2) P.tanh_out[b * LRN_A + j] = th;
-    P.a[k][b * LRN_A + j] = th * P.bound;
-  }
+  store_action(u, P.bound, P.a[k], P.tanh_out, k == 2, b);
 }
 
 struct DaddpgCriticHeadArgs {
@@ -323,10 +349,10 @@ __global__ __launch_bounds__(256) void daddpg_critic_head_kernel(DaddpgCriticHea
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= P.B) return;
   const float4 tw = row4(P.t_W3, 0, lane);
-  const float tq0 = wave_sum(dot4(row4(P.t_h2[0], b, lane), tw)) + P.t_b3[0];
-  const float tq1 = wave_sum(dot4(row4(P.t_h2[1], b, lane), tw)) + P.t_b3[0];
+  const float tq0 = head1(row4(P.t_h2[0], b, lane), tw, P.t_b3);
+  const float tq1 = head1(row4(P.t_h2[1], b, lane), tw, P.t_b3);
   const float4 h = row4(P.h2, b, lane), w = row4(P.W3, 0, lane);
-  const float q = wave_sum(dot4(h, w)) + P.b3[0];
+  const float q = head1(h, w, P.b3);
   const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
   const float target = P.rewards[b] + notdone * P.gamma * fminf(tq0, tq1);
   const float e = q - target;
@@ -335,12 +361,7 @@ __global__ __launch_bounds__(256) void daddpg_critic_head_kernel(DaddpgCriticHea
     P.d3[b] = d3;
     P.loss_rows[b] = e * e;
   }
-  float4 d;
-  d.x = h.x > 0.f ? d3 * w.x : 0.f;
-  d.y = h.y > 0.f ? d3 * w.y : 0.f;
-  d.z = h.z > 0.f ? d3 * w.z : 0.f;
-  d.w = h.w > 0.f ? d3 * w.w : 0.f;
-  reinterpret_cast<float4 *>(P.d2 + b * LRN_H)[lane] = d;
+  store_d2(h, w, d3, P.d2, b, lane);
 }
 
 struct Datd3ActorHeadArgs {
@@ -364,46 +385,22 @@ __global__ __launch_bounds__(256) void datd3_actor_head_kernel(Datd3ActorHeadArg
   const int64_t b = ((int64_t)blockIdx.x - (actor ? nb : 0)) * 4 + (threadIdx.x >> 6);
   if (b >= P.B) return;
   if (actor) {
-    const float4 h = row4(P.h2, b, lane);
     float u[LRN_A];
-#pragma unroll
-    for (int j = 0; j < LRN_A; ++j) u[j] = wave_sum(dot4(h, row4(P.W3, j, lane))) + P.b3[j];
+    head3(P.h2, P.W3, P.b3, b, lane, u);
     if (lane != 0) return;
-#pragma unroll
-    for (int j = 0; j < LRN_A; ++j) {
-      const float th = tanhf(u[j]);
-      P.tanh_out[b * LRN_A + j] = th;
-      P.a[b * LRN_A + j] = th * P.bound;
-    }
+    store_action(u, P.bound, P.a, P.tanh_out, true, b);
     return;
   }
   float u[2][LRN_A];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const float4 h = row4(P.t_h2[i], b, lane);
-#pragma unroll
-    for (int j = 0; j < LRN_A; ++j) u[i][j] = wave_sum(dot4(h, row4(P.t_W3[i], j, lane))) + P.t_b3[i][j];
-  }
+  for (int i = 0; i < 2; ++i) head3(P.t_h2[i], P.t_W3[i], P.t_b3[i], b, lane, u[i]);
   if (lane != 0) return;
-  float z[4];
-  if (P.noise) {
-#pragma unroll
-    for (int j = 0; j < LRN_A; ++j) z[j] = P.noise[b * LRN_A + j];
-  } else {
-    // Philox4x32-10 keyed by seed, counter (row, draw): independent of launch geometry
-    uint32_t c[4] = {(uint32_t)b, (uint32_t)((uint64_t)b >> 32), (uint32_t)P.draw, (uint32_t)(P.draw >> 32)};
-    philox4x32_10(c, (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
-    box_muller(c[0], c[1], z[0], z[1]);
-    box_muller(c[2], c[3], z[2], z[3]);
-  }
+  float nz[LRN_A];
+  row_noise(P.noise, P.seed, P.draw, P.policy_noise, P.noise_clip, b, nz);
 #pragma unroll
   for (int j = 0; j < LRN_A; ++j) {
-    const float nz = fminf(fmaxf(z[j] * P.policy_noise, -P.noise_clip), P.noise_clip);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float v = tanhf(u[i][j]) * P.bound + nz;
-      P.a2[i][b * LRN_A + j] = fminf(fmaxf(v, -P.bound), P.bound);
-    }
+    for (int i = 0; i < 2; ++i) P.a2[i][b * LRN_A + j] = proposal(u[i][j], nz[j], P.bound);
   }
 }
 
@@ -428,10 +425,10 @@ __global__ __launch_bounds__(256) void datd3_critic_head_kernel(Datd3CriticHeadA
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= P.B) return;
-  const float tq0 = wave_sum(dot4(row4(P.t_h2[0], b, lane), row4(P.t_W3[0], 0, lane))) + P.t_b3[0][0];
-  const float tq1 = wave_sum(dot4(row4(P.t_h2[1], b, lane), row4(P.t_W3[1], 0, lane))) + P.t_b3[1][0];
+  const float tq0 = head1(P.t_h2[0], P.t_W3[0], P.t_b3[0], b, lane);
+  const float tq1 = head1(P.t_h2[1], P.t_W3[1], P.t_b3[1], b, lane);
   const float4 h = row4(P.h2, b, lane), w = row4(P.W3, 0, lane);
-  const float q = wave_sum(dot4(h, w)) + P.b3[0];
+  const float q = head1(h, w, P.b3);
   float t = fminf(tq0, tq1);
   if (P.darc) t = P.w_min * t + P.w_max * t;
   const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
@@ -439,7 +436,7 @@ __global__ __launch_bounds__(256) void datd3_critic_head_kernel(Datd3CriticHeadA
   const float e = q - target;
   float d3 = 2.0f * e * P.inv_b;
   if (P.darc) {
-    const float eo = q - (wave_sum(dot4(row4(P.o_h2, b, lane), row4(P.o_W3, 0, lane))) + P.o_b3[0]);
+    const float eo = q - head1(P.o_h2, P.o_W3, P.o_b3, b, lane);
     d3 += P.reg * (2.0f * eo * P.inv_b);
     if (lane == 0) {
       P.loss_rows[2 * b] = e * e;
@@ -449,12 +446,7 @@ __global__ __launch_bounds__(256) void datd3_critic_head_kernel(Datd3CriticHeadA
     P.loss_rows[b] = e * e;
   }
   if (lane == 0) P.d3[b] = d3;
-  float4 d;
-  d.x = h.x > 0.f ? d3 * w.x : 0.f;
-  d.y = h.y > 0.f ? d3 * w.y : 0.f;
-  d.z = h.z > 0.f ? d3 * w.z : 0.f;
-  d.w = h.w > 0.f ? d3 * w.w : 0.f;
-  reinterpret_cast<float4 *>(P.d2 + b * LRN_H)[lane] = d;
+  store_d2(h, w, d3, P.d2, b, lane);
 }
 
 struct ActorBackArgs {
