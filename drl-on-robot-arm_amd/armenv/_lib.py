@@ -85,6 +85,10 @@ class ArmEnvTd3Args(C.Structure):
         + [("workspace_bytes", C.c_int64)])
 
 
+class ArmEnvTd3PopArgs(C.Structure):
+    _fields_ = [("one", ArmEnvTd3Args), ("members", C.c_int32)]
+
+
 class ArmEnvDaddpgArgs(C.Structure):
     _fields_ = (
         [("device", C.c_int32), ("state_dim", C.c_int32), ("action_dim", C.c_int32), ("hidden_dim", C.c_int32), ("batch", C.c_int64)]
@@ -143,6 +147,8 @@ SYMBOLS = {
     "armenv_her_sample": (C.c_int, [C.c_int32, C.POINTER(ArmEnvHerArgs), _P]),
     "armenv_td3_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     "armenv_td3_update": (C.c_int, [C.POINTER(ArmEnvTd3Args), _P]),
+    "armenv_td3_pop_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "armenv_td3_pop_update": (C.c_int, [C.POINTER(ArmEnvTd3PopArgs), _P]),
     "armenv_daddpg_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     "armenv_daddpg_update": (C.c_int, [C.POINTER(ArmEnvDaddpgArgs), _P]),
     "armenv_datd3_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),

@@ -35,6 +35,9 @@
 //  15  gemm   dW1a | db1a partials
 //  16  adam   the stepped actor (6 tensors) + its target's soft update
 // The other critic is read (darc) and never written; the actor's loss never reads a target.
+//
+// armenv_td3_pop_update / armenv_td3_pop_workspace_bytes: the TD3 column for P stacked learners.  The same launches with the
+// *_pop_kernel forms over (workgroups of one member, P); member p's operands lie p member strides behind member 0's (MemberStrides).
 #include <cmath>
 #include <initializer_list>
 
@@ -101,9 +104,37 @@ Feat feat2(const float *p0, int ld0, const float *p1, int ld1, int nf, int64_t r
   return Feat{p0, p1, ld0, ld1, ld0, nf, aug, rows};
 }
 
+// Member strides of a population update (armenv_td3_pop_update): every array of the call is member 0's array of a stack [P][...],
+// so an operand's stride is the size, in elements, of the member-0 array that it points into -- a net or moment tensor, a batch
+// array, or the whole single-learner workspace.  The entry point registers those arrays; of() finds the one that holds a pointer.
+struct MemberStrides {
+  struct Array { uintptr_t lo, hi; int64_t stride; };
+  Array arrays[12 * 6 + 8];
+  int n = 0;
+  int members = 1;
+  int64_t ws = 0;              // the workspace's stride: floats of one single-learner workspace
+  void add(const void *p, int64_t elems, int64_t elem_bytes = sizeof(float)) {
+    if (p) arrays[n++] = Array{(uintptr_t)p, (uintptr_t)p + (uintptr_t)(elems * elem_bytes), elems};
+  }
+  void add(const ArmEnvMlpRW &m, int in, int out) {
+    add(m.W1, (int64_t)LRN_H * in); add(m.b1, LRN_H); add(m.W2, (int64_t)LRN_H * LRN_H); add(m.b2, LRN_H);
+    add(m.W3, (int64_t)out * LRN_H); add(m.b3, out);
+  }
+  // NULL: 0 (an operand that is not read); a pointer outside every registered array: -1
+  int64_t of(const void *p) const {
+    if (!p) return 0;
+    for (int i = 0; i < n; ++i)
+      if ((uintptr_t)p >= arrays[i].lo && (uintptr_t)p < arrays[i].hi) return arrays[i].stride;
+    return -1;
+  }
+};
+
 struct Launcher {
   GemmList L{};
+  GemmStrideList S{};
   int blocks = 0;
+  const MemberStrides *pop = nullptr;    // set: a population update, launched as gemm_pop_kernel over (blocks, members)
+  bool unknown = false;                  // an operand that `pop` cannot place
   void add(const Gemm &g0) {
     Gemm g = g0;
     g.tiles_m = (g.M + LRN_TM - 1) / LRN_TM;
@@ -111,6 +142,12 @@ struct Launcher {
     g.splits = (int)((g.K + g.kchunk - 1) / g.kchunk);
     g.first_block = blocks;
     blocks += g.tiles_m * g.tiles_n * g.splits;
+    if (pop) {
+      GemmStride &t = S.g[L.n];
+      t = GemmStride{pop->of(g.a.p0), pop->of(g.a.p1), pop->of(g.b.p0), pop->of(g.b.p1),
+                     pop->of(g.C),    pop->of(g.bias), pop->of(g.mask), pop->of(g.w)};
+      for (int64_t v : {t.a0, t.a1, t.b0, t.b1, t.C, t.bias, t.mask, t.w}) unknown = unknown || v < 0;
+    }
     L.g[L.n++] = g;
   }
   // Y[B][H] = epilogue(X W^T): X a Feat of B rows and `in` features
@@ -142,7 +179,11 @@ struct Launcher {
     add(g);
   }
   int launch(hipStream_t s) {
-    hipLaunchKernelGGL(gemm_kernel, dim3((unsigned)blocks), dim3(256), 0, s, L);
+    if (unknown) return fail(ARMENV_EINVAL, "fused update: an operand lies outside the population's arrays");
+    if (pop)
+      hipLaunchKernelGGL(gemm_pop_kernel, dim3((unsigned)blocks, (unsigned)pop->members), dim3(256), 0, s, L, S);
+    else
+      hipLaunchKernelGGL(gemm_kernel, dim3((unsigned)blocks), dim3(256), 0, s, L);
     HIP_TRY(hipGetLastError());
     L = GemmList{};
     blocks = 0;
@@ -173,13 +214,16 @@ void adam_tensors(AdamArgs &P, const ArmEnvMlpRW &p, const ArmEnvMlpRW &m, const
 
 // Args: ArmEnvTd3Args, ArmEnvDaddpgArgs or ArmEnvDatd3Args (beta1, beta2, eps, tau)
 template <class Args>
-int launch_adam(AdamArgs &P, float lr, int64_t step, const Args *a, hipStream_t s) {
+int launch_adam(AdamArgs &P, float lr, int64_t step, const Args *a, const MemberStrides *pop, hipStream_t s) {
   P.beta1 = a->beta1; P.beta2 = a->beta2; P.eps = a->eps; P.tau = a->tau;
   const double bc1 = 1.0 - std::pow((double)a->beta1, (double)step), bc2 = 1.0 - std::pow((double)a->beta2, (double)step);
   P.step_size = (float)(lr / bc1);
   P.bc2_sqrt = (float)std::sqrt(bc2);
   const unsigned blocks = (unsigned)((P.total + 255) / 256) + (P.loss_rows ? 1u : 0u);
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, P);
+  if (pop)
+    hipLaunchKernelGGL(adam_pop_kernel, dim3(blocks, (unsigned)pop->members), dim3(256), 0, s, P, pop->ws);
+  else
+    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, P);
   HIP_TRY(hipGetLastError());
   return ARMENV_OK;
 }
@@ -268,12 +312,21 @@ struct Update {
   int loss_cols;               // stage 9: columns of the loss rows
   float loss_w1;               //          and the weight of column 1's mean
   int64_t loss_rows;           //          and where they are in the workspace
+  const MemberStrides *pop;    // a population update: its member count and strides; NULL: one learner, the single-learner kernels
 };
 
 // one launch of a per-row kernel (256 threads: four rows per workgroup)
 template <class Kernel, class KArgs>
 int launch_rows(Kernel kernel, unsigned blocks, const KArgs &args, hipStream_t s) {
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, s, args);
+  HIP_TRY(hipGetLastError());
+  return ARMENV_OK;
+}
+
+// ... and of its population form over (blocks, members)
+template <class Kernel, class KArgs, class KStride>
+int launch_rows_pop(Kernel kernel, unsigned blocks, int members, const KArgs &args, const KStride &strides, hipStream_t s) {
+  hipLaunchKernelGGL(kernel, dim3(blocks, (unsigned)members), dim3(256), 0, s, args, strides);
   HIP_TRY(hipGetLastError());
   return ARMENV_OK;
 }
@@ -292,6 +345,7 @@ int run_update(const Args *a, const Update &u, hipStream_t s, ActorHeads actor_h
   const Feat sa = feat2(a->states_dev, D, a->actions_dev, LRN_A, K1, B);
   auto hidden = [&](int64_t off, int aug = 0) { return feat(ws + off, H, H, B, aug); };
   Launcher L;
+  L.pop = u.pop;
 
   // 1-2: layers 1 and 2 of the target actors, the stepped critics, the stepped actor and the other critic
   for (int i = 0; i < u.n_ta; ++i) L.forward(s2_only, D, u.TA[i]->W1, u.TA[i]->b1, ws + w.ta1[i], B);
@@ -337,7 +391,7 @@ int run_update(const Args *a, const Update &u, hipStream_t s, ActorHeads actor_h
       adam_tensors(P, *u.Q[i].p, *u.Q[i].m, *u.Q[i].v, *u.Q[i].tp, K1, 1, ws + w.pW1[i], ws + w.pW2[i], ws + w.pW3[i]);
     P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = u.critic_soft;
     P.loss_rows = ws + u.loss_rows; P.loss_cols = u.loss_cols; P.loss_w1 = u.loss_w1; P.B = B; P.inv_b = inv_b; P.loss = a->loss_dev;
-    LRN_TRY(launch_adam(P, a->critic_lr, a->critic_step, a, s));
+    LRN_TRY(launch_adam(P, a->critic_lr, a->critic_step, a, u.pop, s));
   }
   if (!with_actor) return ARMENV_OK;
 
@@ -356,7 +410,11 @@ int run_update(const Args *a, const Update &u, hipStream_t s, ActorHeads actor_h
   ActorBackArgs ab{};
   ab.B = B; ab.in_dim = K1; ab.state_dim = D; ab.bound = a->action_bound; ab.dc1 = dc1; ab.Wq1 = Qa.W1;
   ab.tanh_a = ws + w.tanh_a; ab.h2 = ws + w.ah2; ab.W3 = act.W3; ab.du = ws + w.du; ab.da2 = da2;
-  LRN_TRY(launch_rows(actor_back_kernel, row_blocks, ab, s));
+  if (u.pop)
+    LRN_TRY(launch_rows_pop(actor_back_pop_kernel, row_blocks, u.pop->members, ab,
+                            ActorBackStride{u.pop->ws, (int64_t)H * K1, (int64_t)LRN_A * H}, s));
+  else
+    LRN_TRY(launch_rows(actor_back_kernel, row_blocks, ab, s));
 
   // 14-15: the stepped actor's backward and weight-gradient partials (the critics' partials are consumed: same slices)
   L.backward(da2, act.W2, ws + w.ah1, da1, B);
@@ -370,7 +428,7 @@ int run_update(const Args *a, const Update &u, hipStream_t s, ActorHeads actor_h
   AdamArgs P{};
   adam_tensors(P, act, *u.act.m, *u.act.v, *u.act.tp, D, LRN_A, ws + w.pa1, ws + w.pa2, ws + w.pa3);
   P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = 1;
-  return launch_adam(P, a->actor_lr, a->actor_step, a, s);
+  return launch_adam(P, a->actor_lr, a->actor_step, a, u.pop, s);
 }
 
 }  // namespace
@@ -381,8 +439,15 @@ int64_t armenv_td3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_
   return shape_ok(state_dim, hidden_dim, batch) ? bytes_of(layout(batch, 1, 2, false)) : -1;
 }
 
-int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
-  static const char *fn = "armenv_td3_update";
+}  // extern "C"
+
+namespace {
+
+constexpr int kMaxMembers = 64;
+
+// armenv_td3_update (members 1, pop false: the single-learner kernels) and armenv_td3_pop_update (pop true: the population kernels
+// over `members` stacked learners, `a` being member 0's arguments)
+int td3_update(const char *fn, const ArmEnvTd3Args *a, int members, bool pop, const char *ws_fn, void *stream) {
   LRN_TRY(check_sizes(fn, a));
   if (a->with_actor != 0 && a->with_actor != 1) return fail(ARMENV_EINVAL, "%s: with_actor must be 0 or 1", fn);
   if (a->critic_step < 1) return fail(ARMENV_EINVAL, "%s: critic_step must be >= 1", fn);
@@ -391,8 +456,8 @@ int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
       {"actor", &a->actor}, {"q1", &a->q1}, {"q2", &a->q2}, {"target_actor", &a->target_actor}, {"target_q1", &a->target_q1},
       {"target_q2", &a->target_q2}, {"actor_m", &a->actor_m}, {"actor_v", &a->actor_v}, {"q1_m", &a->q1_m}, {"q1_v", &a->q1_v},
       {"q2_m", &a->q2_m}, {"q2_v", &a->q2_v}};
-  LRN_TRY(check_buffers(fn, a, {LRN_NOISE_HP(a)}, {}, nets, armenv_td3_workspace_bytes(a->state_dim, a->hidden_dim, a->batch),
-                        "armenv_td3_workspace_bytes"));
+  const int64_t ws_bytes = armenv_td3_workspace_bytes(a->state_dim, a->hidden_dim, a->batch);
+  LRN_TRY(check_buffers(fn, a, {LRN_NOISE_HP(a)}, {}, nets, ws_bytes * members, ws_fn));
 
   DeviceGuard guard_(a->device);
   if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
@@ -410,6 +475,19 @@ int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
   u.Qa = &a->q1;
   u.critic_soft = a->with_actor; u.loss_cols = 2; u.loss_w1 = 1.0f; u.loss_rows = w.loss2;
 
+  const int D = a->state_dim, K1 = D + LRN_A;
+  MemberStrides ms;
+  if (pop) {
+    ms.members = members;
+    ms.ws = ws_bytes / (int64_t)sizeof(float);
+    ms.add(a->workspace_dev, ms.ws);
+    for (const ArmEnvMlpRW *m : {&a->actor, &a->target_actor, &a->actor_m, &a->actor_v}) ms.add(*m, D, LRN_A);
+    for (const ArmEnvMlpRW *m : {&a->q1, &a->q2, &a->target_q1, &a->target_q2, &a->q1_m, &a->q1_v, &a->q2_m, &a->q2_v}) ms.add(*m, K1, 1);
+    ms.add(a->states_dev, B * D); ms.add(a->next_states_dev, B * D); ms.add(a->actions_dev, B * LRN_A);
+    ms.add(a->rewards_dev, B); ms.add(a->dones_dev, B, 1); ms.add(a->noise_dev, B * LRN_A);
+    u.pop = &ms;
+  }
+
   ActorHeadArgs ah{};
   ah.B = B; ah.t_h2 = ws + w.ta2[0]; ah.t_W3 = a->target_actor.W3; ah.t_b3 = a->target_actor.b3; ah.noise = a->noise_dev;
   ah.seed = a->seed; ah.draw = a->draw; ah.bound = a->action_bound; ah.policy_noise = a->policy_noise; ah.noise_clip = a->noise_clip;
@@ -425,9 +503,39 @@ int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
   }
   ch.loss_rows = ws + u.loss_rows;
 
+  if (pop) {
+    const HeadStride actor_st{ms.ws, (int64_t)LRN_A * LRN_H, LRN_A, B, B * LRN_A}, critic_st{ms.ws, LRN_H, 1, B, 0};
+    return run_update(
+        a, u, s,
+        [&](unsigned row_blocks) {
+          return launch_rows_pop(actor_head_pop_kernel, row_blocks * (a->with_actor ? 2u : 1u), members, ah, actor_st, s);
+        },
+        [&](unsigned row_blocks) { return launch_rows_pop(critic_head_pop_kernel, row_blocks, members, ch, critic_st, s); });
+  }
   return run_update(
       a, u, s, [&](unsigned row_blocks) { return launch_rows(actor_head_kernel, row_blocks * (a->with_actor ? 2u : 1u), ah, s); },
       [&](unsigned row_blocks) { return launch_rows(critic_head_kernel, row_blocks, ch, s); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
+  return td3_update("armenv_td3_update", a, 1, false, "armenv_td3_workspace_bytes", stream);
+}
+
+int64_t armenv_td3_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members) {
+  if (members < 1 || members > kMaxMembers) return -1;
+  const int64_t one = armenv_td3_workspace_bytes(state_dim, hidden_dim, batch);
+  return one < 0 ? -1 : one * members;
+}
+
+int armenv_td3_pop_update(const ArmEnvTd3PopArgs *a, void *stream) {
+  static const char *fn = "armenv_td3_pop_update";
+  if (!a) return fail(ARMENV_EINVAL, "%s: args is NULL", fn);
+  if (a->members < 1 || a->members > kMaxMembers) return fail(ARMENV_EINVAL, "%s: members %d outside 1..%d", fn, (int)a->members, kMaxMembers);
+  return td3_update(fn, &a->one, a->members, true, "armenv_td3_pop_workspace_bytes", stream);
 }
 
 int64_t armenv_daddpg_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch) {

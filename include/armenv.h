@@ -38,6 +38,8 @@ extern "C" {
 #define ARMENV_ABI_VERSION 8   /* 8: + armenv_daddpg_update, armenv_daddpg_workspace_bytes, ArmEnvDaddpgArgs;
                                      still 8: + armenv_datd3_update, armenv_datd3_workspace_bytes, ArmEnvDatd3Args -- purely additive
                                      (two functions, one struct, nothing existing moves), so the number did not change;
+                                     still 8: + armenv_td3_pop_update, armenv_td3_pop_workspace_bytes, ArmEnvTd3PopArgs, additive
+                                     in the same way;
                                   7: + armenv_td3_update, armenv_td3_workspace_bytes, ArmEnvMlpRW, ArmEnvTd3Args;
                                   6: + armenv_set_policy_daddpg, armenv_episode_returns_f32, ARMENV_POLICY_DADDPG; ArmEnvConfig unchanged since 5 */
 
@@ -478,6 +480,30 @@ typedef struct ArmEnvTd3Args {
 /* Bytes of workspace armenv_td3_update needs for (state_dim, hidden_dim, batch); -1 for unsupported sizes. */
 int64_t armenv_td3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch);
 int armenv_td3_update(const ArmEnvTd3Args *args, void *stream);
+
+/* ---- a population of TD3 learners: ONE armenv_td3_update for each of P independent learners ("members") in one launch sequence --
+ * as many launches as for one learner (9, 16 with the actor step), each over P times the workgroups.  Members share the
+ * hyper-parameters, the step numbers (so Adam's bias corrections) and with_actor, and nothing else.
+ *
+ * Stacked tensors: every array that `one` names is member 0's array of a contiguous stack with a leading member dimension, and
+ * member p's array lies p times the array's own size behind it.  There are no stride arguments:
+ *   each of the 6 x 12 net and moment tensors   [P][rows][cols]
+ *   states_dev, next_states_dev [P][B][state_dim];  actions_dev [P][B][3];  rewards_dev, dones_dev [P][B]
+ *   noise_dev (nullable) [P][B][3];  loss_dev (nullable) [P]
+ *   workspace_dev: P consecutive single-learner workspaces (armenv_td3_workspace_bytes is a multiple of 256 bytes)
+ * Noise: member p draws with Philox key seed + p (mod 2^64), counter (row, draw) as armenv_td3_update's, so armenv_td3_update with
+ * seed + p on member p's arrays reproduces member p; noise_dev replaces the draw for all members.
+ * Every sum keeps the single update's order, so member p's results equal, bit for bit, armenv_td3_update on member p's arrays.
+ * Refused before any HIP call (ARMENV_EINVAL, the field named in armenv_last_error()): members outside 1..64, whatever
+ * armenv_td3_update refuses in `one`, and workspace_bytes below armenv_td3_pop_workspace_bytes. */
+typedef struct ArmEnvTd3PopArgs {
+  ArmEnvTd3Args one;   /* member 0's arguments, exactly as armenv_td3_update reads them; workspace_bytes: of all P workspaces */
+  int32_t members;     /* P, 1..64 */
+} ArmEnvTd3PopArgs;
+
+/* members x armenv_td3_workspace_bytes(state_dim, hidden_dim, batch); -1 for unsupported sizes or members outside 1..64. */
+int64_t armenv_td3_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members);
+int armenv_td3_pop_update(const ArmEnvTd3PopArgs *args, void *stream);
 
 /* ---- fused DADDPG learner: one DADDPG_MLP.update (the reference's algo/DADDPG/DADDPG_mlp.py:117-171), the reference's DEFAULT
  * agent (config.py:33), over two actors (fc1-3, tanh x action_bound) and ONE critic over cat(s, a) (fc1-3), hidden_dim 256:
