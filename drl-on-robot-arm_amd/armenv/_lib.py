@@ -116,6 +116,14 @@ class ArmEnvDatd3Args(C.Structure):
         + [("workspace_bytes", C.c_int64)])
 
 
+class ArmEnvDaddpgPopArgs(C.Structure):
+    _fields_ = [("one", ArmEnvDaddpgArgs), ("members", C.c_int32)]
+
+
+class ArmEnvDatd3PopArgs(C.Structure):
+    _fields_ = [("one", ArmEnvDatd3Args), ("members", C.c_int32)]
+
+
 # every symbol include/armenv.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -153,6 +161,10 @@ SYMBOLS = {
     "armenv_daddpg_update": (C.c_int, [C.POINTER(ArmEnvDaddpgArgs), _P]),
     "armenv_datd3_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     "armenv_datd3_update": (C.c_int, [C.POINTER(ArmEnvDatd3Args), _P]),
+    "armenv_daddpg_pop_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "armenv_daddpg_pop_update": (C.c_int, [C.POINTER(ArmEnvDaddpgPopArgs), _P]),
+    "armenv_datd3_pop_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "armenv_datd3_pop_update": (C.c_int, [C.POINTER(ArmEnvDatd3PopArgs), _P]),
     "armenv_probe_issue_rate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "armenv_probe_clock": (C.c_int, [C.c_int32, _P, C.POINTER(C.c_int32), _P]),
     "armenv_num_envs": (C.c_int64, [_P]),

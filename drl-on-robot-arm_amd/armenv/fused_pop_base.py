@@ -1,0 +1,200 @@
+"""What the populations of fused learners (fused_td3_pop.FusedTD3Population, fused_daddpg_pop.FusedDADDPGPopulation,
+fused_datd3_pop.FusedDATD3Population / FusedDARCPopulation) share: the stacks [P][rows][cols] that hold every member's nets and Adam
+moments and the re-pointing of the members' module parameters into them, the stacked batch buffers, the checks of a stacked batch,
+the one call into libarmenv.so (armenv_<algo>_pop_update) and the member-state zip behind load_member / export_member."""
+import ctypes as C
+
+import torch
+
+from . import _lib as L
+from .fused_base import FusedLearner, _mlp_of
+
+MAX_MEMBERS = 64
+
+
+class TwoActorMember:
+    """Member p of a population of two-actor agents: the agent's modules, under the names its single learner gives them, whose
+    parameters are views into the population's stacks (what the update writes, they show; what is written through them, the update
+    reads), with the single learner's ``take_action`` and ``policy_state_dicts()``."""
+
+    _take_action_of_two = FusedLearner._take_action_of_two
+
+    def __init__(self, index, device, names, nets, critics):
+        self.index, self.device = index, device
+        self._names = names
+        for name, net in zip(names, nets):
+            setattr(self, name, net)
+        self._critics = critics            # names of the two critics take_action compares (DADDPG: the one critic twice)
+
+    @property
+    def actor(self):
+        return self.actor1
+
+    def _nets(self):
+        return tuple(getattr(self, n) for n in self._names)
+
+    def take_action(self, state):
+        return self._take_action_of_two(state, getattr(self, self._critics[0]), getattr(self, self._critics[1]))
+
+    def policy_state_dicts(self):
+        """the learning nets that the rollout's fused policy reads, in set_policy_daddpg's / set_policy_datd3's order"""
+        policy = [n for n in self._names if not n.startswith("target_")]
+        return tuple({k: v.detach() for k, v in getattr(self, n).state_dict().items()} for n in policy)
+
+
+class FusedPopulation(FusedLearner):
+    """Base of the populations.  A subclass names its single learner ``_Single`` and its argument struct ``_PopArgs`` (``_Args`` is
+    the struct of `one`), the stacks of its nets ``_NETS`` (ArmEnvMlpRW fields of `one`, in the order of ``_sixes``) and of its
+    moments ``_MOMENTS`` (pairs (moment stack, the net it belongs to)), and the counters ``_COUNTERS`` that are the population's."""
+
+    _Single = _PopArgs = None
+    _NETS = _MOMENTS = _COUNTERS = ()
+
+    def _create(self, members, seed, device, make):
+        """Creates the stacks and the members: member p from the nets of ``torch.manual_seed(seed + p); make("cpu", seed + p)``.
+        The nets are created on the host, where torch's initialisers draw from the CPU generator whatever the device; the global
+        generators are left as found."""
+        if not 1 <= int(members) <= MAX_MEMBERS:
+            raise ValueError("%s: members must be 1..%d" % (type(self).__name__, MAX_MEMBERS))
+        self.members, self.device, self.seed = int(members), torch.device(device), int(seed)
+        cuda = range(torch.cuda.device_count()) if torch.cuda.is_available() and torch.cuda.is_initialized() else []
+        agents = []
+        with torch.random.fork_rng(devices=list(cuda)):
+            for p in range(self.members):
+                torch.manual_seed(self.seed + p)
+                agents.append(make("cpu", self.seed + p))
+        # stacks[name]: six tensors [P][rows][cols] (W1, b1, W2, b2, W3, b3) of net or moment `name`
+        self.stacks = {}
+        for name, six in zip(self._NETS, self._sixes(agents[0])):
+            self.stacks[name] = [torch.empty((self.members,) + tuple(t.shape), dtype=torch.float32, device=self.device) for t in six]
+        for name, net in self._MOMENTS:
+            self.stacks[name] = [torch.zeros_like(t) for t in self.stacks[net]]
+        self._members = []
+        with torch.no_grad():
+            for p, agent in enumerate(agents):
+                for name, six in zip(self._NETS, self._sixes(agent)):
+                    for t, stack in zip(six, self.stacks[name]):
+                        stack[p].copy_(t)
+                        t.data = stack[p]              # the module's parameter becomes the view
+                self._members.append(self._member_of(p, agent))
+        for name in self._COUNTERS:
+            setattr(self, name, 0)
+        self._ws = self._args = self._batch = None
+
+    @staticmethod
+    def _sixes(agent):
+        """the parameters of a single learner's nets, six per entry of _NETS"""
+        return tuple(list(net.parameters()) for net in agent._nets())
+
+    def _member_of(self, p, agent):
+        raise NotImplementedError
+
+    def member(self, p):
+        return self._members[p]
+
+    def batch_buffers(self, batch_size):
+        """the stacked static inputs [P][B][...] of one update; ``member_buffers(p)`` are member p's slices of them"""
+        B, D, P, dev = int(batch_size), self.state_dim, self.members, self.device
+        self._batch = dict(states=torch.zeros(P, B, D, device=dev), actions=torch.zeros(P, B, self.action_dim, device=dev),
+                           next_states=torch.zeros(P, B, D, device=dev), rewards=torch.zeros(P, B, device=dev),
+                           dones=torch.zeros(P, B, dtype=torch.uint8, device=dev))
+        return self._batch
+
+    def member_buffers(self, p):
+        """member p's contiguous slices of the last ``batch_buffers``: the dict that ``TrajectoryStore.sample(out=...)`` fills"""
+        if self._batch is None:
+            raise RuntimeError("%s.member_buffers: call batch_buffers(batch_size) first" % type(self).__name__)
+        return {k: t[p] for k, t in self._batch.items()}
+
+    def _static_args(self):
+        a = self._PopArgs()
+        a.members = self.members
+        one = super()._static_args()
+        for name in self.stacks:
+            setattr(one, name, _mlp_of(self.stacks[name]))
+        a.one = one
+        return a
+
+    def _inputs(self, batch):
+        """(states, actions, rewards, next_states, dones) of a stacked batch dict as the contiguous tensors the update reads"""
+        P, dev = self.members, self.device
+        f32 = lambda k: batch[k].to(dev, torch.float32).contiguous()
+        s, a, s2 = f32("states"), f32("actions"), f32("next_states")
+        if s.dim() != 3 or s.shape[0] != P or s.shape[2] != self.state_dim or a.shape != s.shape[:2] + (self.action_dim,) or s2.shape != s.shape:
+            raise ValueError("%s.train: states / next_states must be [P][B][state_dim] and actions [P][B][action_dim]" % type(self).__name__)
+        B = s.shape[1]
+        r = batch["rewards"].to(dev, torch.float32).reshape(P, B).contiguous()
+        d = batch["dones"].to(dev)
+        d = (d if d.dtype == torch.uint8 else (d != 0).to(torch.uint8)).reshape(P, B).contiguous()
+        return s, a, r, s2, d
+
+    def _noise(self, noise, B):
+        """`noise` as the [P][B][action_dim] f32 device tensor the update reads, or None"""
+        if noise is not None:
+            noise = noise.to(self.device, torch.float32).contiguous()
+            if tuple(noise.shape) != (self.members, B, self.action_dim):
+                raise ValueError("noise must be [P][B][%d] standard normals" % self.action_dim)
+        return noise
+
+    def _workspace(self, B):
+        n = getattr(L.load(), "armenv_%s_workspace_bytes" % self._fn)(self.state_dim, self.hidden_dim, B, self.members)
+        if n < 0:
+            raise ValueError("%s: unsupported batch size %d" % (type(self).__name__, B))
+        if self._ws is None or self._ws.numel() < n:
+            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _call(self, s, a, r, s2, d, noise=None, **per_call):
+        """One armenv_<_fn>_update over prepared stacked tensors on the current stream, with `per_call` written into `one` first;
+        returns the members' critic losses [P] (no host sync)."""
+        B = s.shape[1]
+        ws = self._workspace(B)
+        if self._args is None:
+            self._args = self._static_args()
+        one = self._args.one
+        loss = torch.empty(self.members, dtype=torch.float32, device=self.device)
+        one.batch = B
+        for key, value in per_call.items():
+            setattr(one, key, value)
+        if hasattr(one, "noise_dev"):
+            one.noise_dev = noise.data_ptr() if noise is not None else None
+        one.states_dev, one.actions_dev, one.next_states_dev = s.data_ptr(), a.data_ptr(), s2.data_ptr()
+        one.rewards_dev, one.dones_dev, one.loss_dev = r.data_ptr(), d.data_ptr(), loss.data_ptr()
+        one.workspace_dev, one.workspace_bytes = ws.data_ptr(), ws.numel()
+        update = getattr(L.load(), "armenv_%s_update" % self._fn)
+        L.check(update(C.byref(self._args), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        return loss
+
+    def _member_state(self, p):
+        """member p's parameters and moments as views, six per stack, in _NETS + _MOMENTS order"""
+        return [t[p] for name in self._NETS + tuple(m for m, _ in self._MOMENTS) for t in self.stacks[name]]
+
+    @classmethod
+    def _single_state(cls, agent):
+        """the same tensors of a single learner"""
+        nets = [t for six in cls._sixes(agent) for t in six]
+        return nets + [t for m, _ in cls._MOMENTS for t in getattr(agent, m)]
+
+    def _single(self, device, seed):
+        """a single learner with this population's hyper-parameters"""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def load_member(self, p, agent):
+        """Copies a single learner's whole state into member p: parameters, targets, moments -- and its counters (total_it and the
+        Adam step numbers), which are the population's: load every member from learners at the same step."""
+        for mine, theirs in zip(self._member_state(p), self._single_state(agent)):
+            mine.copy_(theirs)
+        for name in self._COUNTERS:
+            setattr(self, name, getattr(agent, name))
+
+    @torch.no_grad()
+    def export_member(self, p):
+        """a single learner on this device holding member p's whole state, counters and noise seed (``seed + p``) included"""
+        with torch.random.fork_rng(devices=[]):         # its initial weights are overwritten: leave the generator alone
+            agent = self._single(self.device, self.seed + p)
+        for theirs, mine in zip(self._single_state(agent), self._member_state(p)):
+            theirs.copy_(mine)
+        for name in self._COUNTERS:
+            setattr(agent, name, getattr(self, name))
+        return agent

@@ -1,12 +1,16 @@
-"""A population of TD3 agents trained side by side on the device: armenv.train's loop (the reference's train_reach_with_TD3 /
+"""A population of agents trained side by side on the device: armenv.train's loop (the reference's run() / train_reach_with_TD3 /
 train_push_with_TD3 / train_pick_with_TD3) for P independent agents -- a seed sweep -- whose updates are ONE fused HIP update of
-the whole population (armenv.fused_td3_pop.FusedTD3Population) at the reference's own operating point, 40 updates of 256 samples.
+the whole population at the reference's own operating point, 40 updates of 256 samples.  The agent: ``--algo td3`` (the default,
+armenv.fused_td3_pop.FusedTD3Population), ``--algo daddpg`` -- the reference's default agent --
+(armenv.fused_daddpg_pop.FusedDADDPGPopulation), or ``--algo datd3`` / ``--algo darc`` (armenv.fused_datd3_pop), whose one loop
+update is one ``train`` = two reference updates on the batch, as in armenv.train.
 
     python -m armenv.train_pop --members 16 --iterations 200
+    python -m armenv.train_pop --members 16 --iterations 200 --algo daddpg
 
 Member p has its own environments, trajectory store, initial weights and noise, all seeded ``seed + p``.  Rollouts are P launches,
-one per member, each with that member's actor; every update samples each member's store into that member's slice of the stacked
-batch and then runs ONE ``pop.train``.
+one per member, each with that member's policy (TD3: its actor; the two-actor agents: their own take_action, fused into the rollout
+kernel); every update samples each member's store into that member's slice of the stacked batch and then runs ONE ``pop.train``.
 
 Lockstep rule: the members share the step schedule, so an iteration runs its updates only when EVERY member's store is ready (holds
 ``minimal_episodes`` complete episodes); while one member is not, no member is updated.  The members' stores fill at about the same
@@ -18,25 +22,32 @@ import time
 import torch
 
 from . import envs
+from .fused_daddpg_pop import FusedDADDPGPopulation
+from .fused_datd3_pop import FusedDARCPopulation, FusedDATD3Population
 from .fused_td3_pop import FusedTD3Population
 from .replay import TrajectoryStore
 
+ALGOS = ("td3", "daddpg", "datd3", "darc")
+_POPULATIONS = dict(td3=FusedTD3Population, daddpg=FusedDADDPGPopulation, datd3=FusedDATD3Population, darc=FusedDARCPopulation)
 _TASKS = dict(reach=(envs.BatchedReachEnv, 6, 0.7), push=(envs.BatchedPushEnv, 9, 0.4), pick=(envs.BatchedPickEnv, 9, 0.4))
 
 
 def train_reach_population(members=16, num_envs=64, iterations=200, rollout_steps=32, updates=40, batch_size=256, her_ratio=0.8,
                            seed=0, device="cuda:0", actor_kind="actor_f16x3", expl_sigma=None, log_every=10, log=print,
-                           window_steps=1536, minimal_episodes=5, max_steps=500, task="reach"):
+                           window_steps=1536, minimal_episodes=5, max_steps=500, task="reach", algo="td3"):
     """Returns (population, history); a history record holds the members' success rates over the last ``log_every`` iterations.
-    ``task="push" | "pick"``: armenv.train.train_push's settings (state_dim 9, action_bound 0.4, unclipped exploration noise)."""
+    ``task="push" | "pick"``: armenv.train.train_push's settings (state_dim 9, action_bound 0.4, unclipped exploration noise).
+    ``algo``: the agent; the two-actor agents explore as armenv.train has them explore on that task (the same sigma and clip)."""
     if task not in _TASKS:
         raise ValueError("task must be one of %s" % ", ".join(_TASKS))
+    if algo not in ALGOS:
+        raise ValueError("algo must be one of %s" % ", ".join(ALGOS))
     Env, state_dim, action_bound = _TASKS[task]
     reach = task == "reach"
     sigma = expl_sigma if expl_sigma is not None else action_bound * 0.98
     noise_clip = action_bound if reach else 1e9
     P = int(members)
-    pop = FusedTD3Population(P, state_dim, 3, action_bound, device=device, seed=seed)
+    pop = _POPULATIONS[algo](P, state_dim, 3, action_bound, device=device, seed=seed)
     es = [Env(num_envs, device=device, seed=seed + p, max_steps=max_steps) for p in range(P)]
     stores = [TrajectoryStore(device=device, seed=seed + p, capacity_steps=window_steps) for p in range(P)]
     batch = pop.batch_buffers(batch_size)
@@ -48,8 +59,12 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
     t0 = time.perf_counter()
     for it in range(iterations):
         for p, e in enumerate(es):
-            e.set_policy(actor_kind, action_bound=action_bound, noise_sigma=sigma, noise_clip=noise_clip,
-                         actor_state_dict=pop.member(p).actor_state_dict())
+            if algo == "td3":
+                e.set_policy(actor_kind, action_bound=action_bound, noise_sigma=sigma, noise_clip=noise_clip,
+                             actor_state_dict=pop.member(p).actor_state_dict())
+            else:
+                install = dict(daddpg=e.set_policy_daddpg, datd3=e.set_policy_datd3, darc=e.set_policy_darc)[algo]
+                install(*pop.member(p).policy_state_dicts(), action_bound=action_bound, noise_sigma=sigma, noise_clip=noise_clip)
             obs0 = obs[p].clone()
             out = e.rollout(rollout_steps, None, out=bufs[p], want_actions=True, want_terminal_obs=True)
             obs[p] = out["obs"][-1]
@@ -59,7 +74,7 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
             for _ in range(updates):
                 for p, st in enumerate(stores):
                     st.sample(batch_size, use_her=True, her_ratio=her_ratio, out=slices[p])
-                pop.train(batch)
+                pop.train(batch)                          # datd3 / darc: two updates, as the reference's run() counts them
         if (it + 1) % log_every == 0:
             cs = [e.counters() for e in es]
             rates = [(c["successes"] - c0["successes"]) / max(1, c["episodes"] - c0["episodes"]) for c, c0 in zip(cs, prev)]
@@ -76,6 +91,7 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task", default="reach", choices=list(_TASKS))
+    ap.add_argument("--algo", default="td3", choices=list(ALGOS), help="the agent (config.py:33's default is DADDPG_MLP)")
     ap.add_argument("--members", type=int, default=16)
     ap.add_argument("--num-envs", type=int, default=64, help="environments per member")
     ap.add_argument("--iterations", type=int, default=200)
@@ -88,7 +104,7 @@ def main():
     ap.add_argument("--max-steps", type=int, default=500)
     a = ap.parse_args()
     train_reach_population(a.members, a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed,
-                           actor_kind=a.actor, window_steps=a.window_steps, max_steps=a.max_steps, task=a.task)
+                           actor_kind=a.actor, window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, algo=a.algo)
 
 
 if __name__ == "__main__":

@@ -23,9 +23,10 @@
 // draw per row, and the stepped actor's action) and datd3_critic_head_kernel (two target critics, the stepped critic, and with `darc`
 // the mixed target and the pull towards the other critic).
 // No kernel uses atomics, scratch or a memset; nothing is allocated: all intermediates live in the caller's workspace.
-// The five kernels of the TD3 update -- gemm, actor_head, critic_head, actor_back, adam -- are written in armenv_learner_kernels.inc,
-// which the end of this header includes twice: as the single-learner kernels named above and as the *_pop_kernel forms of
-// armenv_td3_pop_update, where a second grid dimension is the member of a population of stacked learners.
+// All nine kernels -- gemm, actor_back, adam and the three updates' actor and critic heads -- are written in
+// armenv_learner_kernels.inc, which the end of this header includes twice: as the single-learner kernels named above and as the
+// *_pop_kernel forms of armenv_td3_pop_update, armenv_daddpg_pop_update and armenv_datd3_pop_update, where a second grid dimension is
+// the member of a population of stacked learners.  This header holds their argument structs and the per-row pieces they are built from.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -203,19 +204,6 @@ struct DaddpgActorHeadArgs {
   float *tanh_out;           // out [B][3]: tanh of problem 2, kept for the backward pass
 };
 
-// blocks [k ceil(B / 4), (k + 1) ceil(B / 4)): rows of problem k; no noise, no clamp (DADDPG_mlp.py:131-134)
-__global__ __launch_bounds__(256) void daddpg_actor_head_kernel(DaddpgActorHeadArgs P) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nb = (P.B + 3) / 4;
-  const int k = (int)((int64_t)blockIdx.x / nb);
-  const int64_t b = ((int64_t)blockIdx.x - k * nb) * 4 + (threadIdx.x >> 6);
-  if (k > 2 || b >= P.B) return;
-  float u[LRN_A];
-  head3(P.h2[k], P.W3[k], P.b3[k], b, lane, u);
-  if (lane != 0) return;
-  store_action(u, P.bound, P.a[k], P.tanh_out, k == 2, b);
-}
-
 struct DaddpgCriticHeadArgs {
   int64_t B;
   float gamma, inv_b;
@@ -229,27 +217,6 @@ struct DaddpgCriticHeadArgs {
   float *loss_rows;                            // out [B]: (q - target)^2
 };
 
-// target = r + (1 - d) gamma min(tq(a2_1), tq(a2_2)); loss = mse(q, target) and its deltas, one wave per row
-__global__ __launch_bounds__(256) void daddpg_critic_head_kernel(DaddpgCriticHeadArgs P) {
-  const int lane = threadIdx.x & 63;
-  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= P.B) return;
-  const float4 tw = row4(P.t_W3, 0, lane);
-  const float tq0 = head1(row4(P.t_h2[0], b, lane), tw, P.t_b3);
-  const float tq1 = head1(row4(P.t_h2[1], b, lane), tw, P.t_b3);
-  const float4 h = row4(P.h2, b, lane), w = row4(P.W3, 0, lane);
-  const float q = head1(h, w, P.b3);
-  const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
-  const float target = P.rewards[b] + notdone * P.gamma * fminf(tq0, tq1);
-  const float e = q - target;
-  const float d3 = 2.0f * e * P.inv_b;
-  if (lane == 0) {
-    P.d3[b] = d3;
-    P.loss_rows[b] = e * e;
-  }
-  store_d2(h, w, d3, P.d2, b, lane);
-}
-
 struct Datd3ActorHeadArgs {
   int64_t B;
   float bound, policy_noise, noise_clip;
@@ -262,33 +229,6 @@ struct Datd3ActorHeadArgs {
   const float *h2, *W3, *b3;
   float *a, *tanh_out;
 };
-
-// blocks [0, ceil(B / 4)): target rows, one wave computes BOTH proposals of its row from one noise draw; the next ceil(B / 4): actor rows
-__global__ __launch_bounds__(256) void datd3_actor_head_kernel(Datd3ActorHeadArgs P) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nb = (P.B + 3) / 4;
-  const bool actor = (int64_t)blockIdx.x >= nb;
-  const int64_t b = ((int64_t)blockIdx.x - (actor ? nb : 0)) * 4 + (threadIdx.x >> 6);
-  if (b >= P.B) return;
-  if (actor) {
-    float u[LRN_A];
-    head3(P.h2, P.W3, P.b3, b, lane, u);
-    if (lane != 0) return;
-    store_action(u, P.bound, P.a, P.tanh_out, true, b);
-    return;
-  }
-  float u[2][LRN_A];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) head3(P.t_h2[i], P.t_W3[i], P.t_b3[i], b, lane, u[i]);
-  if (lane != 0) return;
-  float nz[LRN_A];
-  row_noise(P.noise, P.seed, P.draw, P.policy_noise, P.noise_clip, b, nz);
-#pragma unroll
-  for (int j = 0; j < LRN_A; ++j) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) P.a2[i][b * LRN_A + j] = proposal(u[i][j], nz[j], P.bound);
-  }
-}
 
 struct Datd3CriticHeadArgs {
   int64_t B;
@@ -304,36 +244,6 @@ struct Datd3CriticHeadArgs {
   float *d2;                                   // out [B][H]: (d3 W3) * relu'(h2)
   float *loss_rows;                            // out [B]: (q - target)^2; darc [B][2]: and (q - q_other)^2
 };
-
-// target = r + (1 - d) gamma T, T = min(tq1, tq2) (darc: w_min T + w_max T); loss = mse(q, target) (darc: + reg mse(q, q_other)) and
-// its deltas, one wave per row
-__global__ __launch_bounds__(256) void datd3_critic_head_kernel(Datd3CriticHeadArgs P) {
-  const int lane = threadIdx.x & 63;
-  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= P.B) return;
-  const float tq0 = head1(P.t_h2[0], P.t_W3[0], P.t_b3[0], b, lane);
-  const float tq1 = head1(P.t_h2[1], P.t_W3[1], P.t_b3[1], b, lane);
-  const float4 h = row4(P.h2, b, lane), w = row4(P.W3, 0, lane);
-  const float q = head1(h, w, P.b3);
-  float t = fminf(tq0, tq1);
-  if (P.darc) t = P.w_min * t + P.w_max * t;
-  const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
-  const float target = P.rewards[b] + notdone * P.gamma * t;
-  const float e = q - target;
-  float d3 = 2.0f * e * P.inv_b;
-  if (P.darc) {
-    const float eo = q - head1(P.o_h2, P.o_W3, P.o_b3, b, lane);
-    d3 += P.reg * (2.0f * eo * P.inv_b);
-    if (lane == 0) {
-      P.loss_rows[2 * b] = e * e;
-      P.loss_rows[2 * b + 1] = eo * eo;
-    }
-  } else if (lane == 0) {
-    P.loss_rows[b] = e * e;
-  }
-  if (lane == 0) P.d3[b] = d3;
-  store_d2(h, w, d3, P.d2, b, lane);
-}
 
 struct ActorBackArgs {
   int64_t B;
@@ -373,7 +283,7 @@ struct AdamArgs {
 };
 
 
-// Member strides of the population kernels (armenv_td3_pop_update), in elements per member.  They ride beside the single-learner
+// Member strides of the population kernels (armenv_*_pop_update), in elements per member.  They ride beside the single-learner
 // argument structs, not inside them, so the single-learner kernels keep their arguments.
 struct GemmStride {
   int64_t a0, a1, b0, b1;      // the Feat operands' two bases

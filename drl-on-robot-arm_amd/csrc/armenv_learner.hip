@@ -36,8 +36,9 @@
 //  16  adam   the stepped actor (6 tensors) + its target's soft update
 // The other critic is read (darc) and never written; the actor's loss never reads a target.
 //
-// armenv_td3_pop_update / armenv_td3_pop_workspace_bytes: the TD3 column for P stacked learners.  The same launches with the
-// *_pop_kernel forms over (workgroups of one member, P); member p's operands lie p member strides behind member 0's (MemberStrides).
+// armenv_td3_pop_update, armenv_daddpg_pop_update, armenv_datd3_pop_update and their *_pop_workspace_bytes: the same column for P
+// stacked learners.  The same launches with the *_pop_kernel forms over (workgroups of one member, P); member p's operands lie p
+// member strides behind member 0's (MemberStrides).
 #include <cmath>
 #include <initializer_list>
 
@@ -104,12 +105,12 @@ Feat feat2(const float *p0, int ld0, const float *p1, int ld1, int nf, int64_t r
   return Feat{p0, p1, ld0, ld1, ld0, nf, aug, rows};
 }
 
-// Member strides of a population update (armenv_td3_pop_update): every array of the call is member 0's array of a stack [P][...],
+// Member strides of a population update (armenv_*_pop_update): every array of the call is member 0's array of a stack [P][...],
 // so an operand's stride is the size, in elements, of the member-0 array that it points into -- a net or moment tensor, a batch
 // array, or the whole single-learner workspace.  The entry point registers those arrays; of() finds the one that holds a pointer.
 struct MemberStrides {
   struct Array { uintptr_t lo, hi; int64_t stride; };
-  Array arrays[12 * 6 + 8];
+  Array arrays[16 * 6 + 8];   // DATD3 / DARC: 16 nets and moments of six tensors, the workspace, five batch arrays, the noise
   int n = 0;
   int members = 1;
   int64_t ws = 0;              // the workspace's stride: floats of one single-learner workspace
@@ -542,8 +543,12 @@ int64_t armenv_daddpg_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int
   return shape_ok(state_dim, hidden_dim, batch) ? bytes_of(layout(batch, 2, 1, false)) : -1;
 }
 
-int armenv_daddpg_update(const ArmEnvDaddpgArgs *a, void *stream) {
-  static const char *fn = "armenv_daddpg_update";
+}  // extern "C"
+
+namespace {
+
+// armenv_daddpg_update (members 1, pop false) and armenv_daddpg_pop_update (pop true, `a` being member 0's arguments), as td3_update
+int daddpg_update(const char *fn, const ArmEnvDaddpgArgs *a, int members, bool pop, const char *ws_fn, void *stream) {
   LRN_TRY(check_sizes(fn, a));
   if (a->update_actor != 1 && a->update_actor != 2) return fail(ARMENV_EINVAL, "%s: update_actor %d must be 1 or 2", fn, a->update_actor);
   if (a->critic_step < 1) return fail(ARMENV_EINVAL, "%s: critic_step must be >= 1", fn);
@@ -553,8 +558,8 @@ int armenv_daddpg_update(const ArmEnvDaddpgArgs *a, void *stream) {
       {"target_actor2", &a->target_actor2}, {"target_critic", &a->target_critic}, {"actor1_m", &a->actor1_m},
       {"actor1_v", &a->actor1_v}, {"actor2_m", &a->actor2_m}, {"actor2_v", &a->actor2_v}, {"critic_m", &a->critic_m},
       {"critic_v", &a->critic_v}};
-  LRN_TRY(check_buffers(fn, a, {}, {}, nets, armenv_daddpg_workspace_bytes(a->state_dim, a->hidden_dim, a->batch),
-                        "armenv_daddpg_workspace_bytes"));
+  const int64_t ws_bytes = armenv_daddpg_workspace_bytes(a->state_dim, a->hidden_dim, a->batch);
+  LRN_TRY(check_buffers(fn, a, {}, {}, nets, ws_bytes * members, ws_fn));
 
   DeviceGuard guard_(a->device);
   if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
@@ -585,17 +590,68 @@ int armenv_daddpg_update(const ArmEnvDaddpgArgs *a, void *stream) {
   ch.h2 = ws + w.h2[0]; ch.W3 = a->critic.W3; ch.b3 = a->critic.b3; ch.d3 = ws + w.d3[0]; ch.d2 = ws + w.d2[0];
   ch.loss_rows = ws + u.loss_rows;
 
+  const int D = a->state_dim, K1 = D + LRN_A;
+  MemberStrides ms;
+  if (pop) {
+    ms.members = members;
+    ms.ws = ws_bytes / (int64_t)sizeof(float);
+    ms.add(a->workspace_dev, ms.ws);
+    for (const ArmEnvMlpRW *m : {&a->actor1, &a->actor2, &a->target_actor1, &a->target_actor2, &a->actor1_m, &a->actor1_v, &a->actor2_m,
+                                 &a->actor2_v})
+      ms.add(*m, D, LRN_A);
+    for (const ArmEnvMlpRW *m : {&a->critic, &a->target_critic, &a->critic_m, &a->critic_v}) ms.add(*m, K1, 1);
+    ms.add(a->states_dev, B * D); ms.add(a->next_states_dev, B * D); ms.add(a->actions_dev, B * LRN_A);
+    ms.add(a->rewards_dev, B); ms.add(a->dones_dev, B, 1);
+    u.pop = &ms;
+    const HeadStride actor_st{ms.ws, (int64_t)LRN_A * LRN_H, LRN_A, B, 0}, critic_st{ms.ws, LRN_H, 1, B, 0};
+    return run_update(
+        a, u, s,
+        [&](unsigned row_blocks) { return launch_rows_pop(daddpg_actor_head_pop_kernel, row_blocks * 3u, members, ah, actor_st, s); },
+        [&](unsigned row_blocks) { return launch_rows_pop(daddpg_critic_head_pop_kernel, row_blocks, members, ch, critic_st, s); });
+  }
   return run_update(
       a, u, s, [&](unsigned row_blocks) { return launch_rows(daddpg_actor_head_kernel, row_blocks * 3u, ah, s); },
       [&](unsigned row_blocks) { return launch_rows(daddpg_critic_head_kernel, row_blocks, ch, s); });
+}
+
+// the checks of a *_pop_update entry point's own fields
+template <class PopArgs>
+int check_members(const char *fn, const PopArgs *a) {
+  if (!a) return fail(ARMENV_EINVAL, "%s: args is NULL", fn);
+  if (a->members < 1 || a->members > kMaxMembers) return fail(ARMENV_EINVAL, "%s: members %d outside 1..%d", fn, (int)a->members, kMaxMembers);
+  return ARMENV_OK;
+}
+
+int64_t pop_bytes(int64_t one, int32_t members) { return members < 1 || members > kMaxMembers || one < 0 ? -1 : one * members; }
+
+}  // namespace
+
+extern "C" {
+
+int armenv_daddpg_update(const ArmEnvDaddpgArgs *a, void *stream) {
+  return daddpg_update("armenv_daddpg_update", a, 1, false, "armenv_daddpg_workspace_bytes", stream);
+}
+
+int64_t armenv_daddpg_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members) {
+  return pop_bytes(armenv_daddpg_workspace_bytes(state_dim, hidden_dim, batch), members);
+}
+
+int armenv_daddpg_pop_update(const ArmEnvDaddpgPopArgs *a, void *stream) {
+  static const char *fn = "armenv_daddpg_pop_update";
+  LRN_TRY(check_members(fn, a));
+  return daddpg_update(fn, &a->one, a->members, true, "armenv_daddpg_pop_workspace_bytes", stream);
 }
 
 int64_t armenv_datd3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch) {
   return shape_ok(state_dim, hidden_dim, batch) ? bytes_of(layout(batch, 2, 1, true)) : -1;
 }
 
-int armenv_datd3_update(const ArmEnvDatd3Args *a, void *stream) {
-  static const char *fn = "armenv_datd3_update";
+}  // extern "C"
+
+namespace {
+
+// armenv_datd3_update (members 1, pop false) and armenv_datd3_pop_update (pop true, `a` being member 0's arguments), as td3_update
+int datd3_update(const char *fn, const ArmEnvDatd3Args *a, int members, bool pop, const char *ws_fn, void *stream) {
   LRN_TRY(check_sizes(fn, a));
   if (a->update_actor != 1 && a->update_actor != 2) return fail(ARMENV_EINVAL, "%s: update_actor %d must be 1 or 2", fn, a->update_actor);
   if (a->darc != 0 && a->darc != 1) return fail(ARMENV_EINVAL, "%s: darc %d must be 0 or 1", fn, a->darc);
@@ -609,10 +665,11 @@ int armenv_datd3_update(const ArmEnvDatd3Args *a, void *stream) {
       {"actor2_v", &a->actor2_v}, {"critic1_m", &a->critic1_m}, {"critic1_v", &a->critic1_v}, {"critic2_m", &a->critic2_m},
       {"critic2_v", &a->critic2_v}};
   // q_weight and regularization_weight are read only when darc
+  const int64_t ws_bytes = armenv_datd3_workspace_bytes(a->state_dim, a->hidden_dim, a->batch);
   LRN_TRY(check_buffers(fn, a, {LRN_NOISE_HP(a)},
                         {{"q_weight", darc ? a->q_weight : 0.f, !darc || (a->q_weight >= 0.f && a->q_weight <= 1.f)},
                          {"regularization_weight", darc ? a->regularization_weight : 0.f, !darc || a->regularization_weight >= 0.f}},
-                        nets, armenv_datd3_workspace_bytes(a->state_dim, a->hidden_dim, a->batch), "armenv_datd3_workspace_bytes"));
+                        nets, ws_bytes * members, ws_fn));
 
   DeviceGuard guard_(a->device);
   if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
@@ -654,9 +711,48 @@ int armenv_datd3_update(const ArmEnvDatd3Args *a, void *stream) {
   ch.h2 = ws + w.h2[0]; ch.W3 = u.Q[0].p->W3; ch.b3 = u.Q[0].p->b3; ch.d3 = ws + w.d3[0]; ch.d2 = ws + w.d2[0];
   ch.loss_rows = ws + u.loss_rows;
 
+  const int D = a->state_dim, K1 = D + LRN_A;
+  MemberStrides ms;
+  if (pop) {
+    ms.members = members;
+    ms.ws = ws_bytes / (int64_t)sizeof(float);
+    ms.add(a->workspace_dev, ms.ws);
+    for (const ArmEnvMlpRW *m : {&a->actor1, &a->actor2, &a->target_actor1, &a->target_actor2, &a->actor1_m, &a->actor1_v, &a->actor2_m,
+                                 &a->actor2_v})
+      ms.add(*m, D, LRN_A);
+    for (const ArmEnvMlpRW *m : {&a->critic1, &a->critic2, &a->target_critic1, &a->target_critic2, &a->critic1_m, &a->critic1_v,
+                                 &a->critic2_m, &a->critic2_v})
+      ms.add(*m, K1, 1);
+    ms.add(a->states_dev, B * D); ms.add(a->next_states_dev, B * D); ms.add(a->actions_dev, B * LRN_A);
+    ms.add(a->rewards_dev, B); ms.add(a->dones_dev, B, 1); ms.add(a->noise_dev, B * LRN_A);
+    u.pop = &ms;
+    const HeadStride actor_st{ms.ws, (int64_t)LRN_A * LRN_H, LRN_A, B, B * LRN_A}, critic_st{ms.ws, LRN_H, 1, B, 0};
+    return run_update(
+        a, u, s,
+        [&](unsigned row_blocks) { return launch_rows_pop(datd3_actor_head_pop_kernel, row_blocks * 2u, members, ah, actor_st, s); },
+        [&](unsigned row_blocks) { return launch_rows_pop(datd3_critic_head_pop_kernel, row_blocks, members, ch, critic_st, s); });
+  }
   return run_update(
       a, u, s, [&](unsigned row_blocks) { return launch_rows(datd3_actor_head_kernel, row_blocks * 2u, ah, s); },
       [&](unsigned row_blocks) { return launch_rows(datd3_critic_head_kernel, row_blocks, ch, s); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int armenv_datd3_update(const ArmEnvDatd3Args *a, void *stream) {
+  return datd3_update("armenv_datd3_update", a, 1, false, "armenv_datd3_workspace_bytes", stream);
+}
+
+int64_t armenv_datd3_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members) {
+  return pop_bytes(armenv_datd3_workspace_bytes(state_dim, hidden_dim, batch), members);
+}
+
+int armenv_datd3_pop_update(const ArmEnvDatd3PopArgs *a, void *stream) {
+  static const char *fn = "armenv_datd3_pop_update";
+  LRN_TRY(check_members(fn, a));
+  return datd3_update(fn, &a->one, a->members, true, "armenv_datd3_pop_workspace_bytes", stream);
 }
 
 }  // extern "C"

@@ -1,18 +1,22 @@
-// armenv_learner_kernels.inc -- the five kernels of the fused TD3 update (armenv_learner.h), included twice by that header:
-//   LRN_POP 0   gemm_kernel, actor_head_kernel, critic_head_kernel, actor_back_kernel, adam_kernel: one learner (the DADDPG and
-//               DATD3 / DARC updates share gemm, actor_back and adam)
-//   LRN_POP 1   the *_pop_kernel forms of armenv_td3_pop_update: grid (workgroups of one member, members); member p = blockIdx.y
-//               works on member 0's problem with every operand moved by p times its member stride (in elements), and draws its
-//               target-policy noise with key seed + p.  The strides are a second kernel argument.
+// armenv_learner_kernels.inc -- the nine kernels of the fused updates (armenv_learner.h), included twice by that header:
+//   LRN_POP 0   gemm_kernel, actor_back_kernel, adam_kernel (shared by every update) and the per-row heads actor_head_kernel,
+//               critic_head_kernel (TD3), daddpg_actor_head_kernel, daddpg_critic_head_kernel (DADDPG), datd3_actor_head_kernel,
+//               datd3_critic_head_kernel (DATD3 / DARC): one learner
+//   LRN_POP 1   the *_pop_kernel forms of armenv_td3_pop_update, armenv_daddpg_pop_update and armenv_datd3_pop_update: grid
+//               (workgroups of one member, members); member p = blockIdx.y works on member 0's problem with every operand moved by
+//               p times its member stride (in elements), and draws its target-policy noise with key seed + p.  The strides are a
+//               second kernel argument.
 // One text, two compilations: the population form is a compile-time variant, the single-learner kernels hold no member arithmetic,
 // and both run the same operations in the same order, which is what makes member p of a population update equal the single update
 // bit for bit.
 #if LRN_POP
 #define LRN_KERNEL(name) name##_pop_kernel
 #define LRN_POP_PARAM(decl) , decl
+#define LRN_MEMBER(ptr, stride) ((ptr) + (int64_t)blockIdx.y * (stride))     // member blockIdx.y's `ptr`
 #else
 #define LRN_KERNEL(name) name##_kernel
 #define LRN_POP_PARAM(decl)
+#define LRN_MEMBER(ptr, stride) ptr
 #endif
 
 __global__ __launch_bounds__(256) void LRN_KERNEL(gemm)(GemmList L LRN_POP_PARAM(GemmStrideList S)) {
@@ -166,6 +170,128 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(critic_head)(CriticHeadArgs P 
   }
 }
 
+// DADDPG.  blocks [k ceil(B / 4), (k + 1) ceil(B / 4)): rows of problem k; no noise, no clamp (DADDPG_mlp.py:131-134).  The
+// population form moves problem k's pointers where it reads them (LRN_MEMBER): shifting the argument's arrays in place and then
+// indexing them by k would put them in scratch.
+__global__ __launch_bounds__(256) void LRN_KERNEL(daddpg_actor_head)(DaddpgActorHeadArgs P LRN_POP_PARAM(HeadStride S)) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nb = (P.B + 3) / 4;
+  const int k = (int)((int64_t)blockIdx.x / nb);
+  const int64_t b = ((int64_t)blockIdx.x - k * nb) * 4 + (threadIdx.x >> 6);
+  if (k > 2 || b >= P.B) return;
+  float u[LRN_A];
+  head3(LRN_MEMBER(P.h2[k], S.ws), LRN_MEMBER(P.W3[k], S.W3), LRN_MEMBER(P.b3[k], S.b3), b, lane, u);
+  if (lane != 0) return;
+  store_action(u, P.bound, LRN_MEMBER(P.a[k], S.ws), LRN_MEMBER(P.tanh_out, S.ws), k == 2, b);
+}
+
+// DADDPG.  target = r + (1 - d) gamma min(tq(a2_1), tq(a2_2)); loss = mse(q, target) and its deltas, one wave per row
+__global__ __launch_bounds__(256) void LRN_KERNEL(daddpg_critic_head)(DaddpgCriticHeadArgs P LRN_POP_PARAM(HeadStride S)) {
+#if LRN_POP
+  {
+    const int64_t p = blockIdx.y;
+    P.rewards += p * S.rows; P.dones += p * S.rows;
+    P.t_h2[0] += p * S.ws; P.t_h2[1] += p * S.ws; P.h2 += p * S.ws; P.d3 += p * S.ws; P.d2 += p * S.ws; P.loss_rows += p * S.ws;
+    P.t_W3 += p * S.W3; P.W3 += p * S.W3; P.t_b3 += p * S.b3; P.b3 += p * S.b3;
+  }
+#endif
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= P.B) return;
+  const float4 tw = row4(P.t_W3, 0, lane);
+  const float tq0 = head1(row4(P.t_h2[0], b, lane), tw, P.t_b3);
+  const float tq1 = head1(row4(P.t_h2[1], b, lane), tw, P.t_b3);
+  const float4 h = row4(P.h2, b, lane), w = row4(P.W3, 0, lane);
+  const float q = head1(h, w, P.b3);
+  const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
+  const float target = P.rewards[b] + notdone * P.gamma * fminf(tq0, tq1);
+  const float e = q - target;
+  const float d3 = 2.0f * e * P.inv_b;
+  if (lane == 0) {
+    P.d3[b] = d3;
+    P.loss_rows[b] = e * e;
+  }
+  store_d2(h, w, d3, P.d2, b, lane);
+}
+
+// DATD3 / DARC.  blocks [0, ceil(B / 4)): target rows, one wave computes BOTH proposals of its row from one noise draw; the next
+// ceil(B / 4): actor rows
+__global__ __launch_bounds__(256) void LRN_KERNEL(datd3_actor_head)(Datd3ActorHeadArgs P LRN_POP_PARAM(HeadStride S)) {
+#if LRN_POP
+  {
+    const int64_t p = blockIdx.y;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { P.t_h2[i] += p * S.ws; P.a2[i] += p * S.ws; P.t_W3[i] += p * S.W3; P.t_b3[i] += p * S.b3; }
+    P.h2 += p * S.ws; P.a += p * S.ws; P.tanh_out += p * S.ws; P.W3 += p * S.W3; P.b3 += p * S.b3;
+    if (P.noise) P.noise += p * S.noise;
+    P.seed += (uint64_t)p;     // member p's Philox key; the counter (row, draw) is the single form's
+  }
+#endif
+  const int lane = threadIdx.x & 63;
+  const int64_t nb = (P.B + 3) / 4;
+  const bool actor = (int64_t)blockIdx.x >= nb;
+  const int64_t b = ((int64_t)blockIdx.x - (actor ? nb : 0)) * 4 + (threadIdx.x >> 6);
+  if (b >= P.B) return;
+  if (actor) {
+    float u[LRN_A];
+    head3(P.h2, P.W3, P.b3, b, lane, u);
+    if (lane != 0) return;
+    store_action(u, P.bound, P.a, P.tanh_out, true, b);
+    return;
+  }
+  float u[2][LRN_A];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) head3(P.t_h2[i], P.t_W3[i], P.t_b3[i], b, lane, u[i]);
+  if (lane != 0) return;
+  float nz[LRN_A];
+  row_noise(P.noise, P.seed, P.draw, P.policy_noise, P.noise_clip, b, nz);
+#pragma unroll
+  for (int j = 0; j < LRN_A; ++j) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) P.a2[i][b * LRN_A + j] = proposal(u[i][j], nz[j], P.bound);
+  }
+}
+
+// DATD3 / DARC.  target = r + (1 - d) gamma T, T = min(tq1, tq2) (darc: w_min T + w_max T); loss = mse(q, target) (darc: + reg
+// mse(q, q_other)) and its deltas, one wave per row
+__global__ __launch_bounds__(256) void LRN_KERNEL(datd3_critic_head)(Datd3CriticHeadArgs P LRN_POP_PARAM(HeadStride S)) {
+#if LRN_POP
+  {
+    const int64_t p = blockIdx.y;
+    P.rewards += p * S.rows; P.dones += p * S.rows;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { P.t_h2[i] += p * S.ws; P.t_W3[i] += p * S.W3; P.t_b3[i] += p * S.b3; }
+    P.h2 += p * S.ws; P.d3 += p * S.ws; P.d2 += p * S.ws; P.loss_rows += p * S.ws; P.W3 += p * S.W3; P.b3 += p * S.b3;
+    if (P.darc) { P.o_h2 += p * S.ws; P.o_W3 += p * S.W3; P.o_b3 += p * S.b3; }     // NULL without darc
+  }
+#endif
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= P.B) return;
+  const float tq0 = head1(P.t_h2[0], P.t_W3[0], P.t_b3[0], b, lane);
+  const float tq1 = head1(P.t_h2[1], P.t_W3[1], P.t_b3[1], b, lane);
+  const float4 h = row4(P.h2, b, lane), w = row4(P.W3, 0, lane);
+  const float q = head1(h, w, P.b3);
+  float t = fminf(tq0, tq1);
+  if (P.darc) t = P.w_min * t + P.w_max * t;
+  const float notdone = 1.0f - (P.dones[b] ? 1.0f : 0.0f);
+  const float target = P.rewards[b] + notdone * P.gamma * t;
+  const float e = q - target;
+  float d3 = 2.0f * e * P.inv_b;
+  if (P.darc) {
+    const float eo = q - head1(P.o_h2, P.o_W3, P.o_b3, b, lane);
+    d3 += P.reg * (2.0f * eo * P.inv_b);
+    if (lane == 0) {
+      P.loss_rows[2 * b] = e * e;
+      P.loss_rows[2 * b + 1] = eo * eo;
+    }
+  } else if (lane == 0) {
+    P.loss_rows[b] = e * e;
+  }
+  if (lane == 0) P.d3[b] = d3;
+  store_d2(h, w, d3, P.d2, b, lane);
+}
+
 // back through cat(s, a) -> a = bound tanh(u) -> fc3 of the actor, one wave per row
 __global__ __launch_bounds__(256) void LRN_KERNEL(actor_back)(ActorBackArgs P LRN_POP_PARAM(ActorBackStride S)) {
 #if LRN_POP
@@ -272,4 +398,5 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(adam)(AdamArgs P LRN_POP_PARAM
 #undef LRN_LOSS_ROWS
 #undef LRN_LOSS
 #undef LRN_KERNEL
+#undef LRN_MEMBER
 #undef LRN_POP_PARAM

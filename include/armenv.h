@@ -40,6 +40,8 @@ extern "C" {
                                      (two functions, one struct, nothing existing moves), so the number did not change;
                                      still 8: + armenv_td3_pop_update, armenv_td3_pop_workspace_bytes, ArmEnvTd3PopArgs, additive
                                      in the same way;
+                                     still 8: + armenv_daddpg_pop_update, armenv_datd3_pop_update, their *_pop_workspace_bytes and
+                                     ArmEnvDaddpgPopArgs / ArmEnvDatd3PopArgs, additive in the same way;
                                   7: + armenv_td3_update, armenv_td3_workspace_bytes, ArmEnvMlpRW, ArmEnvTd3Args;
                                   6: + armenv_set_policy_daddpg, armenv_episode_returns_f32, ARMENV_POLICY_DADDPG; ArmEnvConfig unchanged since 5 */
 
@@ -586,6 +588,38 @@ typedef struct ArmEnvDatd3Args {
 /* Bytes of workspace armenv_datd3_update needs for (state_dim, hidden_dim, batch), darc or not; -1 for unsupported sizes. */
 int64_t armenv_datd3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch);
 int armenv_datd3_update(const ArmEnvDatd3Args *args, void *stream);
+
+/* ---- populations of DADDPG and of DATD3 / DARC learners: ONE armenv_daddpg_update / armenv_datd3_update for each of P independent
+ * learners ("members") in the launch sequence of one update -- 16 launches, each over P times the workgroups.  The contract is
+ * ArmEnvTd3PopArgs' (above): `one` is member 0's arguments exactly as the single entry point reads them, and every array it names
+ * is member 0's slice of a contiguous stack [P][...] with no stride arguments --
+ *   each of the 6 x 12 (DADDPG) or 6 x 16 (DATD3 / DARC) net and moment tensors   [P][rows][cols]
+ *   states_dev, next_states_dev [P][B][state_dim];  actions_dev [P][B][3];  rewards_dev, dones_dev [P][B]
+ *   noise_dev (DATD3 / DARC, nullable) [P][B][3];  loss_dev (nullable) [P]
+ *   workspace_dev: P consecutive single-learner workspaces
+ * Members share the hyper-parameters, update_actor, darc, q_weight, regularization_weight and both step numbers, and nothing else.
+ * DATD3 / DARC: member p draws its noise with Philox key seed + p (mod 2^64) and the unchanged counter (row, draw), once per row for
+ * both proposals.  Every sum keeps the single update's order, so member p's results equal, bit for bit, the single entry point on
+ * member p's arrays (DATD3 / DARC: with seed + p).
+ * Refused before any HIP call (ARMENV_EINVAL, the field named in armenv_last_error()): NULL args, members outside 1..64, whatever
+ * the single entry point refuses in `one`, and workspace_bytes below the *_pop_workspace_bytes of the call. */
+typedef struct ArmEnvDaddpgPopArgs {
+  ArmEnvDaddpgArgs one;   /* member 0's arguments; workspace_bytes: of all P workspaces */
+  int32_t members;        /* P, 1..64 */
+} ArmEnvDaddpgPopArgs;
+
+/* members x armenv_daddpg_workspace_bytes(state_dim, hidden_dim, batch); -1 for unsupported sizes or members outside 1..64. */
+int64_t armenv_daddpg_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members);
+int armenv_daddpg_pop_update(const ArmEnvDaddpgPopArgs *args, void *stream);
+
+typedef struct ArmEnvDatd3PopArgs {
+  ArmEnvDatd3Args one;    /* member 0's arguments; workspace_bytes: of all P workspaces */
+  int32_t members;        /* P, 1..64 */
+} ArmEnvDatd3PopArgs;
+
+/* members x armenv_datd3_workspace_bytes(state_dim, hidden_dim, batch); -1 for unsupported sizes or members outside 1..64. */
+int64_t armenv_datd3_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members);
+int armenv_datd3_pop_update(const ArmEnvDatd3PopArgs *args, void *stream);
 
 /* Measurement aid (bench.py's roofline.valu.one_wave_per_simd; no reference counterpart): the interval at which SIMDs issue
  * independent 64-lane v_fma_f64 (precision 64) / v_fma_f32 (32) instructions when every SIMD of `device` holds
