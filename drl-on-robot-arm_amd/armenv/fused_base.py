@@ -1,6 +1,8 @@
-"""What the fused learners (fused_td3.FusedTD3, fused_daddpg.FusedDADDPG, fused_datd3.FusedDATD3 / FusedDARC) share: the ArmEnvMlpRW
-views of their nets, the batch and workspace tensors, the argument struct's common part and the one call into libarmenv.so."""
+"""What the fused learners (fused_td3.FusedTD3, fused_daddpg.FusedDADDPG, fused_datd3.FusedDATD3 / FusedDARC) and their populations
+share: the ArmEnvMlpRW views of their nets, the stored hyper-parameters, the batch and workspace tensors, the argument struct's common
+part and the one call into libarmenv.so."""
 import ctypes as C
+from functools import cached_property
 
 import torch
 
@@ -26,18 +28,39 @@ def _mlp_of(tensors):
 
 
 class FusedLearner:
-    """Base of the fused learners.  A subclass names its C entry points (``_fn`` of armenv_<_fn>_update and
-    armenv_<_fn>_workspace_bytes), its argument struct ``_Args``, the hyper-parameters ``_hyper`` it copies into it beside the
-    common ones, and which exception ``_noise_error`` a wrongly shaped ``noise`` raises; it creates its own nets, in its torch
-    learner's order."""
+    """Base of the fused learners and, through fused_pop_base.FusedPopulation, of their populations.  An agent's schedule class (the
+    mixin next to its single learner: fused_td3.TD3Schedule, ...) names the C entry points' argument struct ``_Args``, the
+    hyper-parameters ``_hyper`` it copies into the struct beside the common ones, the constructor's hyper-parameters ``_HYPER_KW``
+    and the host counters ``_COUNTERS``, and holds ``train``; the learner names its entry points (``_fn`` of armenv_<_fn>_update and
+    armenv_<_fn>_workspace_bytes) and which exception ``_noise_error`` a wrongly shaped ``noise`` raises, and creates its own nets,
+    in its torch learner's order.  What a population overrides of the call path: ``_lead``, the shape in front of every tensor -- ()
+    here, (P,) there: the loss's shape, what precedes [B][action_dim] in `noise`, and the workspace query's further argument --,
+    ``_batch_axis`` (which axis of the batch is B, ``len(_lead)``) and ``_per_call_struct``."""
 
     _fn = _Args = None
-    _hyper = ()
+    _hyper = _HYPER_KW = _COUNTERS = ()       # _hyper: fields of the C struct; _HYPER_KW: keyword arguments of the constructor
+    _takes_seed = False                       # whether the constructor has `seed` (the agent draws target-policy noise)
     _noise_error = ValueError
+    _lead, _batch_axis = (), 0
 
     def _check_shapes(self, state_dim, action_dim, hidden_dim):
         if hidden_dim != 256 or action_dim != 3 or not 1 <= state_dim <= 12:
             raise ValueError("%s: the fused update is built for hidden_dim 256, action_dim 3, state_dim 1..12" % type(self).__name__)
+
+    def _configure(self, state_dim, action_dim, action_bound, **hyper):
+        """What the constructors of an agent's single learner and of its population share: the shape check, the shapes, the agent's
+        hyper-parameters (every name of ``_HYPER_KW``) and Adam's constants as attributes, the counters at 0, nothing bound yet."""
+        if set(hyper) != set(self._HYPER_KW):                     # a population's **darc may carry a name its agent does not take
+            raise TypeError("%s: hyper-parameters missing: %s; not taken: %s" % (type(self).__name__, sorted(set(self._HYPER_KW) - set(hyper)),
+                                                                                 sorted(set(hyper) - set(self._HYPER_KW))))
+        self._check_shapes(state_dim, action_dim, hyper["hidden_dim"])
+        self.state_dim, self.action_dim, self.action_bound = state_dim, action_dim, action_bound
+        for name, value in hyper.items():
+            setattr(self, name, value)
+        self.betas, self.eps = (0.9, 0.999), 1e-8                 # torch.optim.Adam's defaults, as the torch learners' optimisers
+        for name in self._COUNTERS:
+            setattr(self, name, 0)
+        self._ws = self._args = self._one = None                  # _one: the per-call struct inside _args, set where _args is
 
     def _static_args(self):
         """the part of the argument struct that does not change between updates: what every update has; a subclass adds its nets"""
@@ -58,8 +81,18 @@ class FusedLearner:
                     next_states=torch.zeros(B, D, device=dev), rewards=torch.zeros(B, device=dev),
                     dones=torch.zeros(B, dtype=torch.uint8, device=dev))
 
+    @cached_property
+    def _update_fn(self):
+        return getattr(L.load(), "armenv_%s_update" % self._fn)
+
+    @cached_property
+    def _workspace_fn(self):
+        return getattr(L.load(), "armenv_%s_workspace_bytes" % self._fn)
+
     def _workspace(self, B):
-        n = getattr(L.load(), "armenv_%s_workspace_bytes" % self._fn)(self.state_dim, self.hidden_dim, B)
+        """the workspace of an update of B rows (kept, and grown when needed); an unsupported batch size raises ValueError.  The
+        schedules call this before they move a counter, so a refused batch leaves the learner as it was."""
+        n = self._workspace_fn(self.state_dim, self.hidden_dim, B, *self._lead)
         if n < 0:
             raise ValueError("%s: unsupported batch size %d" % (type(self).__name__, B))
         if self._ws is None or self._ws.numel() < n:
@@ -76,32 +109,40 @@ class FusedLearner:
         return f32("states"), f32("actions"), r, f32("next_states"), d
 
     def _noise(self, noise, B):
-        """`noise` as the [B][action_dim] f32 device tensor the update reads, or None"""
+        """`noise` as the [B][action_dim] ([P][B][action_dim]) f32 device tensor the update reads, or None"""
         if noise is not None:
             noise = noise.to(self.device, torch.float32).contiguous()
-            if tuple(noise.shape) != (B, self.action_dim):
-                raise self._noise_error("noise must be [B][%d] standard normals" % self.action_dim)
+            if tuple(noise.shape) != self._lead + (B, self.action_dim):
+                raise self._noise_error("noise must be %s[B][%d] standard normals" % ("[P]" * len(self._lead), self.action_dim))
         return noise
 
-    def _call(self, s, a, r, s2, d, noise=None, **per_call):
-        """One armenv_<_fn>_update over prepared tensors on the current stream, with `per_call` (step numbers, which nets, draw)
-        written into the argument struct first; returns the critic loss as a 0-dim tensor (no host sync)."""
+    @staticmethod
+    def _per_call_struct(args):
+        """the struct of `args` that holds what changes between updates"""
+        return args
+
+    def _bind(self, args):
+        """makes `args` the argument struct of the updates to come"""
+        self._args, self._one = args, self._per_call_struct(args)
+        self._has_noise = hasattr(self._one, "noise_dev")
+
+    def _call(self, ws, s, a, r, s2, d, noise=None, **per_call):
+        """One armenv_<_fn>_update over prepared tensors and the workspace `ws` on the current stream, with `per_call` (step numbers,
+        which nets, draw) written into the argument struct first; returns the critic loss (no host sync): a 0-dim tensor, [P] from a
+        population."""
         if self._args is None:
-            self._args = self._static_args()
-        args = self._args
-        B = s.shape[0]
-        ws = self._workspace(B)
-        loss = torch.empty((), dtype=torch.float32, device=self.device)
-        args.batch = B
+            self._bind(self._static_args())
+        one = self._one
+        loss = torch.empty(self._lead, dtype=torch.float32, device=self.device)
+        one.batch = s.shape[self._batch_axis]
         for key, value in per_call.items():
-            setattr(args, key, value)
-        if hasattr(args, "noise_dev"):
-            args.noise_dev = noise.data_ptr() if noise is not None else None
-        args.states_dev, args.actions_dev, args.next_states_dev = s.data_ptr(), a.data_ptr(), s2.data_ptr()
-        args.rewards_dev, args.dones_dev, args.loss_dev = r.data_ptr(), d.data_ptr(), loss.data_ptr()
-        args.workspace_dev, args.workspace_bytes = ws.data_ptr(), ws.numel()
-        update = getattr(L.load(), "armenv_%s_update" % self._fn)
-        L.check(update(C.byref(args), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            setattr(one, key, value)
+        if self._has_noise:
+            one.noise_dev = noise.data_ptr() if noise is not None else None
+        one.states_dev, one.actions_dev, one.next_states_dev = s.data_ptr(), a.data_ptr(), s2.data_ptr()
+        one.rewards_dev, one.dones_dev, one.loss_dev = r.data_ptr(), d.data_ptr(), loss.data_ptr()
+        one.workspace_dev, one.workspace_bytes = ws.data_ptr(), ws.numel()
+        L.check(self._update_fn(C.byref(self._args), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         return loss
 
     @torch.no_grad()

@@ -13,15 +13,42 @@ from .policies import QValueNet
 from .td3 import Actor
 
 
-class FusedDADDPG(FusedLearner):
+class DADDPGSchedule:
+    """DADDPG's step schedule, written once for FusedDADDPG and fused_daddpg_pop.FusedDADDPGPopulation: the hyper-parameters, the host
+    counters and ``train``, in terms of the base's ``_inputs``, ``_workspace`` and ``_call``."""
+
+    _Args = L.ArmEnvDaddpgArgs
+    _HYPER_KW = ("hidden_dim", "actor_lr", "critic_lr", "tau", "gamma")
+    _COUNTERS = ("total_it", "critic_step", "actor1_step", "actor2_step")
+
+    def train(self, batch):
+        """One update from a dict of device tensors: states [B,D], actions [B,3], next_states [B,D], rewards [B], dones [B] (any
+        dtype).  Returns the critic loss as a 0-dim tensor (no host sync).  A population updates every member: each tensor stacked
+        under a leading [P], the critic losses [P].  A batch size that is refused raises before a counter moves."""
+        inputs = self._inputs(batch)
+        ws = self._workspace(inputs[0].shape[self._batch_axis])
+        self.total_it += 1
+        update_a1 = self.total_it % 2 == 0                        # DADDPG_mlp.py:119
+        loss = self._call(ws, *inputs, critic_step=self.critic_step + 1, update_actor=1 if update_a1 else 2,
+                          actor_step=(self.actor1_step if update_a1 else self.actor2_step) + 1)
+        self.critic_step += 1
+        if update_a1:
+            self.actor1_step += 1
+        else:
+            self.actor2_step += 1
+        return loss
+
+
+class FusedDADDPG(DADDPGSchedule, FusedLearner):
     """armenv.daddpg.DADDPG's constructor and public surface (``train(batch)``, ``total_it``, the six modules, the ``actor`` property,
     ``take_action``, ``policy_state_dicts()``, ``_nets()``) with the update in HIP; ``load_from`` copies a DADDPG's whole state."""
 
-    _fn, _Args = "daddpg", L.ArmEnvDaddpgArgs
+    _fn = "daddpg"
 
     def __init__(self, state_dim, action_dim, action_bound, hidden_dim=256, actor_lr=1e-3, critic_lr=1e-3, tau=0.005, gamma=0.98,
                  device="cuda:0"):
-        self._check_shapes(state_dim, action_dim, hidden_dim)
+        self._configure(state_dim, action_dim, action_bound, hidden_dim=hidden_dim, actor_lr=actor_lr, critic_lr=critic_lr, tau=tau,
+                        gamma=gamma)
         self.device = torch.device(device)
         mk_a = lambda: Actor(state_dim, hidden_dim, action_dim, action_bound).to(self.device)
         mk_q = lambda: QValueNet(state_dim, hidden_dim, action_dim).to(self.device)
@@ -33,18 +60,11 @@ class FusedDADDPG(FusedLearner):
             t_.load_state_dict(n_.state_dict())
         for n in self._nets():
             n.requires_grad_(False)
-        self.state_dim, self.action_dim, self.hidden_dim = state_dim, action_dim, hidden_dim
-        self.actor_lr, self.critic_lr, self.tau, self.gamma, self.action_bound = actor_lr, critic_lr, tau, gamma, action_bound
-        self.betas, self.eps = (0.9, 0.999), 1e-8                 # torch.optim.Adam's defaults, as DADDPG's optimisers
         # Adam moments in parameters() order of each learning net
         zeros = lambda net: [torch.zeros_like(p) for p in net.parameters()]
         self.actor1_m, self.actor1_v = zeros(self.actor1), zeros(self.actor1)
         self.actor2_m, self.actor2_v = zeros(self.actor2), zeros(self.actor2)
         self.critic_m, self.critic_v = zeros(self.critic), zeros(self.critic)
-        self.critic_step = self.actor1_step = self.actor2_step = 0
-        self.total_it = 0
-        self._ws = None
-        self._args = None
 
     @property
     def actor(self):
@@ -62,21 +82,6 @@ class FusedDADDPG(FusedLearner):
             setattr(a, name + "_m", _mlp_of(getattr(self, name + "_m")))
             setattr(a, name + "_v", _mlp_of(getattr(self, name + "_v")))
         return a
-
-    def train(self, batch):
-        """One update from a dict of device tensors: states [B,D], actions [B,3], next_states [B,D], rewards [B], dones [B] (any
-        dtype).  Returns the critic loss as a 0-dim tensor (no host sync)."""
-        inputs = self._inputs(batch)
-        self.total_it += 1
-        update_a1 = self.total_it % 2 == 0                        # DADDPG_mlp.py:119
-        loss = self._call(*inputs, critic_step=self.critic_step + 1, update_actor=1 if update_a1 else 2,
-                          actor_step=(self.actor1_step if update_a1 else self.actor2_step) + 1)
-        self.critic_step += 1
-        if update_a1:
-            self.actor1_step += 1
-        else:
-            self.actor2_step += 1
-        return loss
 
     def load_from(self, daddpg):
         """Copies parameters, Adam moments, the three step counters and total_it from an armenv.daddpg.DADDPG (identical state for

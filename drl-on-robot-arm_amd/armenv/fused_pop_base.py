@@ -1,12 +1,10 @@
 """What the populations of fused learners (fused_td3_pop.FusedTD3Population, fused_daddpg_pop.FusedDADDPGPopulation,
 fused_datd3_pop.FusedDATD3Population / FusedDARCPopulation) share: the stacks [P][rows][cols] that hold every member's nets and Adam
 moments and the re-pointing of the members' module parameters into them, the stacked batch buffers, the checks of a stacked batch,
-the one call into libarmenv.so (armenv_<algo>_pop_update) and the member-state zip behind load_member / export_member."""
-import ctypes as C
-
+what differs in FusedLearner's one call into libarmenv.so (armenv_<algo>_pop_update) and the member-state zip behind load_member /
+export_member.  The step schedule is the agent's own, shared with its single learner (fused_td3.TD3Schedule, ...)."""
 import torch
 
-from . import _lib as L
 from .fused_base import FusedLearner, _mlp_of
 
 MAX_MEMBERS = 64
@@ -45,24 +43,26 @@ class TwoActorMember:
 class FusedPopulation(FusedLearner):
     """Base of the populations.  A subclass names its single learner ``_Single`` and its argument struct ``_PopArgs`` (``_Args`` is
     the struct of `one`), the stacks of its nets ``_NETS`` (ArmEnvMlpRW fields of `one`, in the order of ``_sixes``) and of its
-    moments ``_MOMENTS`` (pairs (moment stack, the net it belongs to)), and the counters ``_COUNTERS`` that are the population's."""
+    moments ``_MOMENTS`` (pairs (moment stack, the net it belongs to)); the schedule's counters ``_COUNTERS`` are the population's."""
 
     _Single = _PopArgs = None
-    _NETS = _MOMENTS = _COUNTERS = ()
+    _NETS = _MOMENTS = ()
+    _batch_axis = 1
 
-    def _create(self, members, seed, device, make):
-        """Creates the stacks and the members: member p from the nets of ``torch.manual_seed(seed + p); make("cpu", seed + p)``.
+    def _create(self, members, seed, device):
+        """Creates the stacks and the members: member p from the nets of ``torch.manual_seed(seed + p); _single("cpu", seed + p)``.
         The nets are created on the host, where torch's initialisers draw from the CPU generator whatever the device; the global
         generators are left as found."""
         if not 1 <= int(members) <= MAX_MEMBERS:
             raise ValueError("%s: members must be 1..%d" % (type(self).__name__, MAX_MEMBERS))
         self.members, self.device, self.seed = int(members), torch.device(device), int(seed)
+        self._lead = (self.members,)
         cuda = range(torch.cuda.device_count()) if torch.cuda.is_available() and torch.cuda.is_initialized() else []
         agents = []
         with torch.random.fork_rng(devices=list(cuda)):
             for p in range(self.members):
                 torch.manual_seed(self.seed + p)
-                agents.append(make("cpu", self.seed + p))
+                agents.append(self._single("cpu", self.seed + p))
         # stacks[name]: six tensors [P][rows][cols] (W1, b1, W2, b2, W3, b3) of net or moment `name`
         self.stacks = {}
         for name, six in zip(self._NETS, self._sixes(agents[0])):
@@ -77,9 +77,7 @@ class FusedPopulation(FusedLearner):
                         stack[p].copy_(t)
                         t.data = stack[p]              # the module's parameter becomes the view
                 self._members.append(self._member_of(p, agent))
-        for name in self._COUNTERS:
-            setattr(self, name, 0)
-        self._ws = self._args = self._batch = None
+        self._batch = None
 
     @staticmethod
     def _sixes(agent):
@@ -128,42 +126,9 @@ class FusedPopulation(FusedLearner):
         d = (d if d.dtype == torch.uint8 else (d != 0).to(torch.uint8)).reshape(P, B).contiguous()
         return s, a, r, s2, d
 
-    def _noise(self, noise, B):
-        """`noise` as the [P][B][action_dim] f32 device tensor the update reads, or None"""
-        if noise is not None:
-            noise = noise.to(self.device, torch.float32).contiguous()
-            if tuple(noise.shape) != (self.members, B, self.action_dim):
-                raise ValueError("noise must be [P][B][%d] standard normals" % self.action_dim)
-        return noise
-
-    def _workspace(self, B):
-        n = getattr(L.load(), "armenv_%s_workspace_bytes" % self._fn)(self.state_dim, self.hidden_dim, B, self.members)
-        if n < 0:
-            raise ValueError("%s: unsupported batch size %d" % (type(self).__name__, B))
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._ws
-
-    def _call(self, s, a, r, s2, d, noise=None, **per_call):
-        """One armenv_<_fn>_update over prepared stacked tensors on the current stream, with `per_call` written into `one` first;
-        returns the members' critic losses [P] (no host sync)."""
-        B = s.shape[1]
-        ws = self._workspace(B)
-        if self._args is None:
-            self._args = self._static_args()
-        one = self._args.one
-        loss = torch.empty(self.members, dtype=torch.float32, device=self.device)
-        one.batch = B
-        for key, value in per_call.items():
-            setattr(one, key, value)
-        if hasattr(one, "noise_dev"):
-            one.noise_dev = noise.data_ptr() if noise is not None else None
-        one.states_dev, one.actions_dev, one.next_states_dev = s.data_ptr(), a.data_ptr(), s2.data_ptr()
-        one.rewards_dev, one.dones_dev, one.loss_dev = r.data_ptr(), d.data_ptr(), loss.data_ptr()
-        one.workspace_dev, one.workspace_bytes = ws.data_ptr(), ws.numel()
-        update = getattr(L.load(), "armenv_%s_update" % self._fn)
-        L.check(update(C.byref(self._args), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
-        return loss
+    @staticmethod
+    def _per_call_struct(args):
+        return args.one
 
     def _member_state(self, p):
         """member p's parameters and moments as views, six per stack, in _NETS + _MOMENTS order"""
@@ -176,8 +141,11 @@ class FusedPopulation(FusedLearner):
         return nets + [t for m, _ in cls._MOMENTS for t in getattr(agent, m)]
 
     def _single(self, device, seed):
-        """a single learner with this population's hyper-parameters"""
-        raise NotImplementedError
+        """a single learner with this population's hyper-parameters, and `seed` where the agent takes one"""
+        kw = {name: getattr(self, name) for name in self._HYPER_KW}
+        if self._takes_seed:
+            kw["seed"] = seed
+        return self._Single(self.state_dim, self.action_dim, self.action_bound, device=device, **kw)
 
     @torch.no_grad()
     def load_member(self, p, agent):

@@ -12,18 +12,47 @@ from .fused_base import FusedLearner, _mlp, _mlp_of  # noqa: F401  (_mlp, _mlp_o
 from .td3 import Actor, TwinCritic
 
 
-class FusedTD3(FusedLearner):
+class TD3Schedule:
+    """TD3's step schedule, written once for FusedTD3 and fused_td3_pop.FusedTD3Population: the hyper-parameters, the host counters and
+    ``train``, in terms of the base's ``_inputs``, ``_noise``, ``_workspace`` and ``_call``."""
+
+    _Args = L.ArmEnvTd3Args
+    _hyper = ("policy_noise", "noise_clip", "seed")
+    _takes_seed = True
+    _HYPER_KW = ("hidden_dim", "actor_lr", "critic_lr", "tau", "gamma", "policy_noise", "noise_clip", "policy_freq")
+    _COUNTERS = ("total_it", "critic_step", "actor_step")
+
+    def train(self, batch, noise=None):
+        """One update from a dict of device tensors: states [B,D], actions [B,3], next_states [B,D], rewards [B], dones [B] (any
+        dtype).  `noise` (optional): [B,3] standard normals for the target-policy noise.  Returns the critic loss as a 0-dim tensor
+        (no host sync).  A population updates every member: each tensor stacked under a leading [P], the critic losses [P].  A batch
+        size or a `noise` that is refused raises before a counter moves."""
+        inputs = self._inputs(batch)
+        B = inputs[0].shape[self._batch_axis]
+        noise = self._noise(noise, B)
+        ws = self._workspace(B)
+        self.total_it += 1
+        with_actor = self.total_it % self.policy_freq == 0          # delayed actor + soft updates, TD3_mlp.py:144
+        loss = self._call(ws, *inputs, noise, critic_step=self.critic_step + 1, actor_step=self.actor_step + 1 if with_actor else 0,
+                          with_actor=int(with_actor), draw=self.total_it)
+        self.critic_step += 1
+        if with_actor:
+            self.actor_step += 1
+        return loss
+
+
+class FusedTD3(TD3Schedule, FusedLearner):
     """armenv.td3.TD3's constructor and public surface (``train(batch)``, ``total_it``, ``actor_state_dict()``, ``take_action``, the
     ``actor`` / ``critic`` / ``target_actor`` / ``target_critic`` modules) with the update in HIP.  ``seed`` keys the in-kernel
     target-policy noise (Philox4x32-10 over (seed, row, update number)); ``train(batch, noise=...)`` supplies it instead."""
 
-    _fn, _Args = "td3", L.ArmEnvTd3Args
-    _hyper, _noise_error = ("policy_noise", "noise_clip", "seed"), AssertionError
+    _fn, _noise_error = "td3", AssertionError
 
     def __init__(self, state_dim, action_dim, action_bound, hidden_dim=256, actor_lr=1e-3, critic_lr=1e-3, tau=0.005,
                  gamma=0.98, policy_noise=0.2, noise_clip=0.5, policy_freq=3, device="cuda:0", seed=0):
-        self._check_shapes(state_dim, action_dim, hidden_dim)
-        self.device = torch.device(device)
+        self._configure(state_dim, action_dim, action_bound, hidden_dim=hidden_dim, actor_lr=actor_lr, critic_lr=critic_lr, tau=tau,
+                        gamma=gamma, policy_noise=policy_noise, noise_clip=noise_clip, policy_freq=policy_freq)
+        self.device, self.seed = torch.device(device), int(seed)
         self.actor = Actor(state_dim, hidden_dim, action_dim, action_bound).to(self.device)       # TD3's creation order
         self.critic = TwinCritic(state_dim, hidden_dim, action_dim).to(self.device)
         self.target_actor = Actor(state_dim, hidden_dim, action_dim, action_bound).to(self.device)
@@ -32,20 +61,11 @@ class FusedTD3(FusedLearner):
         self.target_actor.load_state_dict(self.actor.state_dict())
         for n in self._nets():
             n.requires_grad_(False)
-        self.state_dim, self.action_dim, self.hidden_dim = state_dim, action_dim, hidden_dim
-        self.actor_lr, self.critic_lr, self.tau, self.gamma, self.action_bound = actor_lr, critic_lr, tau, gamma, action_bound
-        self.policy_noise, self.noise_clip, self.policy_freq = policy_noise, noise_clip, policy_freq
-        self.betas, self.eps = (0.9, 0.999), 1e-8                 # torch.optim.Adam's defaults, as TD3's optimisers
-        self.seed = int(seed)
         # Adam moments in parameters() order of the actor and of the critic
         self.actor_m = [torch.zeros_like(p) for p in self.actor.parameters()]
         self.actor_v = [torch.zeros_like(p) for p in self.actor.parameters()]
         self.critic_m = [torch.zeros_like(p) for p in self.critic.parameters()]
         self.critic_v = [torch.zeros_like(p) for p in self.critic.parameters()]
-        self.actor_step = self.critic_step = 0
-        self.total_it = 0
-        self._ws = None
-        self._args = None
 
     def _nets(self):
         return (self.actor, self.critic, self.target_actor, self.target_critic)
@@ -61,21 +81,6 @@ class FusedTD3(FusedLearner):
         a.q1_m, a.q1_v = _mlp_of(self.critic_m[:6]), _mlp_of(self.critic_v[:6])
         a.q2_m, a.q2_v = _mlp_of(self.critic_m[6:]), _mlp_of(self.critic_v[6:])
         return a
-
-    def train(self, batch, noise=None):
-        """One update from a dict of device tensors: states [B,D], actions [B,3], next_states [B,D], rewards [B], dones [B] (any
-        dtype).  `noise` (optional): [B,3] standard normals for the target-policy noise.  Returns the critic loss as a 0-dim tensor
-        (no host sync)."""
-        inputs = self._inputs(batch)
-        noise = self._noise(noise, inputs[0].shape[0])
-        self.total_it += 1
-        with_actor = self.total_it % self.policy_freq == 0          # delayed actor + soft updates, TD3_mlp.py:144
-        loss = self._call(*inputs, noise, critic_step=self.critic_step + 1, actor_step=self.actor_step + 1 if with_actor else 0,
-                          with_actor=int(with_actor), draw=self.total_it)
-        self.critic_step += 1
-        if with_actor:
-            self.actor_step += 1
-        return loss
 
     def load_from(self, td3):
         """Copies parameters, Adam moments, step counters and total_it from an armenv.td3.TD3 (identical state for comparisons)."""

@@ -31,6 +31,8 @@ from .td3 import TD3
 
 ALGOS = ("td3", "daddpg", "datd3", "darc")
 _TORCH = dict(td3=TD3, daddpg=DADDPG, datd3=DATD3, darc=DARC)
+# --task: the environment, its state_dim and the action bound (main.py:87, :455-457); armenv.train_pop reads it too
+_TASKS = dict(reach=(envs.BatchedReachEnv, 6, 0.7), push=(envs.BatchedPushEnv, 9, 0.4), pick=(envs.BatchedPickEnv, 9, 0.4))
 
 
 def _check_learner(algo, learner):
@@ -57,47 +59,38 @@ def _make_agent(algo, learner, state_dim, action_bound, device, batch_size, use_
     return agent, static, use_graphs
 
 
-def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, batch_size=2048, her_ratio=0.8, seed=0,
-                device="cuda:0", actor_kind="actor_f16x3", expl_sigma=0.7 * 0.98, log_every=10, log=print,
-                window_steps=1536, minimal_episodes=5, max_steps=500, use_graphs=True, algo="td3", learner="torch"):
-    # learner="hip": the TD3 update is libarmenv's fused one (armenv.fused_td3.FusedTD3), issued directly: no capture, no graph.
-    # learner="fused": the agent's own fused update -- FusedTD3 for td3, armenv.fused_daddpg.FusedDADDPG for daddpg,
-    # armenv.fused_datd3.FusedDATD3 / FusedDARC for datd3 / darc.
-    # use_graphs: the agent's update replayed from hipGraphs (GraphedLearner.capture): the update is ~130 small kernels, launch-bound
-    # when issued one by one (160 iterations: 7 s against 14 s).  Round 6 found the replayed updates no longer learning and why: a
-    # hipMemsetAsync captured into a hipGraph works on the first replay only on this ROCm build, torch's multi-block reductions
-    # initialise their semaphores with one, so every captured bias gradient went wrong from the second replay on.  The captured update
-    # now contains no such reduction (armenv.td3._CaptureSafeLinear; profiles/r06_td3_hipgraph_learning.txt) and learns like the eager one.
+def _install_policy(env, algo, agent, actor_kind, action_bound, sigma, clip):
+    """take_action + exploration noise of `agent` (a learner, or a member of a population) as the fused policy of `env`'s rollouts
+    (main.py:114-124): TD3's actor as `actor_kind`, the two-actor agents' own take_action"""
+    if algo == "td3":
+        env.set_policy(actor_kind, action_bound=action_bound, noise_sigma=sigma, noise_clip=clip, actor_state_dict=agent.actor_state_dict())
+    else:
+        install = dict(daddpg=env.set_policy_daddpg, datd3=env.set_policy_datd3, darc=env.set_policy_darc)[algo]
+        install(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=sigma, noise_clip=clip)
+
+
+def _train(Env, state_dim, action_bound, sigma, clip, num_envs, iterations, rollout_steps, updates, batch_size, her_ratio, seed, device,
+           actor_kind, log_every, log, window_steps, minimal_episodes, max_steps, use_graphs, algo, learner):
+    """The loop behind train_reach and train_push: a task's environment class, state_dim and action_bound (a row of ``_TASKS``) and its
+    exploration noise N(0, sigma) clipped at `clip`."""
     _check_learner(algo, learner)
     torch.manual_seed(seed)
-    action_bound = 0.7                                            # main.py:87
-    env = envs.BatchedReachEnv(num_envs, device=device, seed=seed, max_steps=max_steps)
-    agent, static, use_graphs = _make_agent(algo, learner, 6, action_bound, device, batch_size, use_graphs, seed)  # main.py:93
+    env = Env(num_envs, device=device, seed=seed, max_steps=max_steps)
+    agent, static, use_graphs = _make_agent(algo, learner, state_dim, action_bound, device, batch_size, use_graphs, seed)  # main.py:93
     store = TrajectoryStore(device=device, seed=seed, capacity_steps=window_steps)   # last `window_steps` steps of every env
-    ready = False
     obs = env.reset()
-    history = []
+    history, bufs = [], {}
     c_prev = env.counters()
     t0 = time.perf_counter()
-    bufs = {}
     for it in range(iterations):
-        # take_action + exploration noise + step, fused (main.py:114-124)
-        if algo == "daddpg":
-            env.set_policy_daddpg(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=expl_sigma, noise_clip=action_bound)
-        elif algo in ("datd3", "darc"):
-            install = env.set_policy_darc if algo == "darc" else env.set_policy_datd3
-            install(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=expl_sigma, noise_clip=action_bound)
-        else:
-            env.set_policy(actor_kind, action_bound=action_bound, noise_sigma=expl_sigma, noise_clip=action_bound,
-                           actor_state_dict=agent.actor_state_dict())
+        _install_policy(env, algo, agent, actor_kind, action_bound, sigma, clip)
         obs0 = obs.clone()
         out = env.rollout(rollout_steps, None, out=bufs, want_actions=True, want_terminal_obs=True)
         obs = out["obs"][-1]
         store.add_rollout(obs0, out, starts_at_reset=(it == 0))    # traj.store_step / add_trajectory (main.py:128-129)
         # replay_buffer.size() >= minimal_episodes (main.py:135), re-checked every iteration: the ring window can lose its
         # complete episodes again, and the sampler then returns inert all-zero batches that must not be trained on
-        ready = store.size() >= minimal_episodes
-        if ready:
+        if store.size() >= minimal_episodes:
             for _ in range(updates):                              # main.py:136-138
                 if use_graphs:     # HER batch written straight into the captured update's static buffers
                     agent.train_graphed(store.sample(batch_size, use_her=True, her_ratio=her_ratio, out=static))
@@ -118,6 +111,23 @@ def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, bat
     return agent, history
 
 
+def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, batch_size=2048, her_ratio=0.8, seed=0,
+                device="cuda:0", actor_kind="actor_f16x3", expl_sigma=0.7 * 0.98, log_every=10, log=print,
+                window_steps=1536, minimal_episodes=5, max_steps=500, use_graphs=True, algo="td3", learner="torch"):
+    # learner="hip": the TD3 update is libarmenv's fused one (armenv.fused_td3.FusedTD3), issued directly: no capture, no graph.
+    # learner="fused": the agent's own fused update -- FusedTD3 for td3, armenv.fused_daddpg.FusedDADDPG for daddpg,
+    # armenv.fused_datd3.FusedDATD3 / FusedDARC for datd3 / darc.
+    # use_graphs: the agent's update replayed from hipGraphs (GraphedLearner.capture): the update is ~130 small kernels, launch-bound
+    # when issued one by one (160 iterations: 7 s against 14 s).  Round 6 found the replayed updates no longer learning and why: a
+    # hipMemsetAsync captured into a hipGraph works on the first replay only on this ROCm build, torch's multi-block reductions
+    # initialise their semaphores with one, so every captured bias gradient went wrong from the second replay on.  The captured update
+    # now contains no such reduction (armenv.td3._CaptureSafeLinear; profiles/r06_td3_hipgraph_learning.txt) and learns like the eager one.
+    # Exploration noise N(0, expl_sigma) clipped at the action bound, 0.7.
+    Env, state_dim, action_bound = _TASKS["reach"]
+    return _train(Env, state_dim, action_bound, expl_sigma, action_bound, num_envs, iterations, rollout_steps, updates, batch_size,
+                  her_ratio, seed, device, actor_kind, log_every, log, window_steps, minimal_episodes, max_steps, use_graphs, algo, learner)
+
+
 def train_push(num_envs=1024, iterations=300, rollout_steps=32, updates=48, batch_size=2048, her_ratio=0.8, seed=0,
                device="cuda:0", actor_kind="actor_f16x3", log_every=10, log=print, window_steps=1536, minimal_episodes=5,
                max_steps=500, task="push", use_graphs=True, algo="td3", learner="torch"):
@@ -125,54 +135,14 @@ def train_push(num_envs=1024, iterations=300, rollout_steps=32, updates=48, batc
     unclipped exploration noise N(0, 0.4 * 0.98) (:484), push HER relabel rule (utils/rl_utils.py:171-188).  The cube
     follows the build's simplified push-out model, so learning curves are not comparable with the reference's.
     ``task="pick"`` is ``train_pick_with_TD3`` (main.py:518-585), the same loop around RLPickEnv."""
-    _check_learner(algo, learner)
-    torch.manual_seed(seed)
-    action_bound = 0.4
-    Env = envs.BatchedPushEnv if task == "push" else envs.BatchedPickEnv
-    env = Env(num_envs, device=device, seed=seed, max_steps=max_steps)
-    agent, static, use_graphs = _make_agent(algo, learner, 9, action_bound, device, batch_size, use_graphs, seed)
-    store = TrajectoryStore(device=device, seed=seed, capacity_steps=window_steps)
-    obs = env.reset()
-    history, ready, bufs = [], False, {}
-    c_prev = env.counters()
-    t0 = time.perf_counter()
-    for it in range(iterations):
-        if algo == "daddpg":
-            env.set_policy_daddpg(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=action_bound * 0.98, noise_clip=1e9)
-        elif algo in ("datd3", "darc"):
-            install = env.set_policy_darc if algo == "darc" else env.set_policy_datd3
-            install(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=action_bound * 0.98, noise_clip=1e9)
-        else:
-            env.set_policy(actor_kind, action_bound=action_bound, noise_sigma=action_bound * 0.98, noise_clip=1e9,
-                           actor_state_dict=agent.actor_state_dict())
-        obs0 = obs.clone()
-        out = env.rollout(rollout_steps, None, out=bufs, want_actions=True, want_terminal_obs=True)
-        obs = out["obs"][-1]
-        store.add_rollout(obs0, out, starts_at_reset=(it == 0))
-        ready = store.size() >= minimal_episodes         # re-checked every iteration, see train_reach
-        if ready:
-            for _ in range(updates):
-                if use_graphs:     # HER batch written straight into the captured update's static buffers
-                    agent.train_graphed(store.sample(batch_size, use_her=True, her_ratio=her_ratio, out=static))
-                elif static is not None:     # fused learner: HER batch written into its static input buffers
-                    agent.train(store.sample(batch_size, use_her=True, her_ratio=her_ratio, out=static))
-                else:
-                    agent.train(store.sample(batch_size, use_her=True, her_ratio=her_ratio))
-        if (it + 1) % log_every == 0:
-            c = env.counters()
-            ep = c["episodes"] - c_prev["episodes"]
-            rec = dict(iteration=it + 1, env_steps=c["env_steps"], episodes=c["episodes"],
-                       success_rate=(c["successes"] - c_prev["successes"]) / max(1, ep), wall_s=time.perf_counter() - t0)
-            c_prev = c
-            history.append(rec)
-            log(json.dumps(rec))
-    env.close()
-    return agent, history
+    Env, state_dim, action_bound = _TASKS["push" if task == "push" else "pick"]
+    return _train(Env, state_dim, action_bound, action_bound * 0.98, 1e9, num_envs, iterations, rollout_steps, updates, batch_size,
+                  her_ratio, seed, device, actor_kind, log_every, log, window_steps, minimal_episodes, max_steps, use_graphs, algo, learner)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--task", default="reach", choices=["reach", "push", "pick"])
+    ap.add_argument("--task", default="reach", choices=list(_TASKS))
     ap.add_argument("--num-envs", type=int, default=1024)
     ap.add_argument("--iterations", type=int, default=200)
     ap.add_argument("--rollout-steps", type=int, default=32)

@@ -19,17 +19,13 @@ import argparse
 import json
 import time
 
-import torch
-
-from . import envs
 from .fused_daddpg_pop import FusedDADDPGPopulation
 from .fused_datd3_pop import FusedDARCPopulation, FusedDATD3Population
 from .fused_td3_pop import FusedTD3Population
 from .replay import TrajectoryStore
+from .train import _TASKS, ALGOS, _install_policy
 
-ALGOS = ("td3", "daddpg", "datd3", "darc")
 _POPULATIONS = dict(td3=FusedTD3Population, daddpg=FusedDADDPGPopulation, datd3=FusedDATD3Population, darc=FusedDARCPopulation)
-_TASKS = dict(reach=(envs.BatchedReachEnv, 6, 0.7), push=(envs.BatchedPushEnv, 9, 0.4), pick=(envs.BatchedPickEnv, 9, 0.4))
 
 
 def train_reach_population(members=16, num_envs=64, iterations=200, rollout_steps=32, updates=40, batch_size=256, her_ratio=0.8,
@@ -43,9 +39,8 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
     if algo not in ALGOS:
         raise ValueError("algo must be one of %s" % ", ".join(ALGOS))
     Env, state_dim, action_bound = _TASKS[task]
-    reach = task == "reach"
     sigma = expl_sigma if expl_sigma is not None else action_bound * 0.98
-    noise_clip = action_bound if reach else 1e9
+    noise_clip = action_bound if task == "reach" else 1e9
     P = int(members)
     pop = _POPULATIONS[algo](P, state_dim, 3, action_bound, device=device, seed=seed)
     es = [Env(num_envs, device=device, seed=seed + p, max_steps=max_steps) for p in range(P)]
@@ -59,12 +54,7 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
     t0 = time.perf_counter()
     for it in range(iterations):
         for p, e in enumerate(es):
-            if algo == "td3":
-                e.set_policy(actor_kind, action_bound=action_bound, noise_sigma=sigma, noise_clip=noise_clip,
-                             actor_state_dict=pop.member(p).actor_state_dict())
-            else:
-                install = dict(daddpg=e.set_policy_daddpg, datd3=e.set_policy_datd3, darc=e.set_policy_darc)[algo]
-                install(*pop.member(p).policy_state_dicts(), action_bound=action_bound, noise_sigma=sigma, noise_clip=noise_clip)
+            _install_policy(e, algo, pop.member(p), actor_kind, action_bound, sigma, noise_clip)
             obs0 = obs[p].clone()
             out = e.rollout(rollout_steps, None, out=bufs[p], want_actions=True, want_terminal_obs=True)
             obs[p] = out["obs"][-1]

@@ -287,6 +287,44 @@ def test_unsupported_shapes_raise(kind, kw):
         Pop(a["members"], a["state_dim"], a["action_dim"], 0.7, hidden_dim=a["hidden_dim"], device="cpu")
 
 
+@pytest.mark.parametrize("algo", ("td3", "daddpg", "datd3", "darc"))
+def test_a_refused_call_leaves_every_counter_at_zero(algo):
+    """A batch of 0 rows, which the workspace query refuses, and a `noise` of the wrong shape raise from `train` (DATD3 / DARC: from
+    `update` too) before total_it or a step number moves -- in the single learner as in a population.  No device is touched."""
+    from armenv.fused_td3 import FusedTD3
+    from armenv.fused_td3_pop import FusedTD3Population
+    Pop, Single = (FusedTD3Population, FusedTD3) if algo == "td3" else _classes(algo)[:2]
+    two_updates = algo in ("datd3", "darc")
+    for learner, lead in ((Single(6, 3, 0.7, device="cpu"), ()), (Pop(2, 6, 3, 0.7, device="cpu"), (2,))):
+        def batch(B):
+            return dict(states=torch.zeros(*lead, B, 6), actions=torch.zeros(*lead, B, 3), next_states=torch.zeros(*lead, B, 6),
+                        rewards=torch.zeros(*lead, B), dones=torch.zeros(*lead, B, dtype=torch.uint8))
+
+        def counters():
+            return {k: v for k, v in vars(learner).items() if k == "total_it" or k.endswith("_step")}
+        assert set(counters()) == set(learner._COUNTERS) and len(counters()) == dict(td3=3, daddpg=4, datd3=5, darc=5)[algo]
+        assert tuple(batch(0)["states"].shape) == lead + (0, 6)
+        calls = [lambda: learner.train(batch(0))]
+        if two_updates:
+            calls += [lambda: learner.update(batch(0)), lambda: learner.update(batch(0), update_a1=False)]
+        for call in calls:
+            with pytest.raises(ValueError):
+                call()
+            assert all(v == 0 for v in counters().values()), counters()
+        if algo == "daddpg":
+            continue                                            # takes no noise
+        # TD3's single learner keeps the AssertionError it always raised for this
+        error = AssertionError if isinstance(learner, FusedTD3) else ValueError
+        good, bad = torch.zeros(*lead, 4, 3), torch.zeros(*lead, 5, 3)
+        calls = [lambda: learner.train(batch(4), noise=(good, bad) if two_updates else bad)]
+        if two_updates:
+            calls += [lambda: learner.train(batch(4), noise=(bad, good)), lambda: learner.update(batch(4), noise=bad)]
+        for call in calls:
+            with pytest.raises(error):
+                call()
+            assert all(v == 0 for v in counters().values()), counters()
+
+
 def test_train_pop_refuses_an_unknown_agent():
     from armenv.train_pop import ALGOS as algos, train_reach_population
     assert algos == ("td3", "daddpg", "datd3", "darc")
