@@ -67,6 +67,10 @@ class ArmEnvHerArgs(C.Structure):
     ]
 
 
+class ArmEnvHerPopArgs(C.Structure):
+    _fields_ = [("one", ArmEnvHerArgs), ("members", C.c_int32), ("episodes_stride", C.c_int64)]
+
+
 class ArmEnvMlpRW(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("W1", "b1", "W2", "b2", "W3", "b3")]
 
@@ -153,6 +157,10 @@ SYMBOLS = {
     "armenv_count_episodes": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P]),
     "armenv_write_episodes": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, _P, _P]),
     "armenv_her_sample": (C.c_int, [C.c_int32, C.POINTER(ArmEnvHerArgs), _P]),
+    "armenv_her_pop_sample": (C.c_int, [C.c_int32, C.POINTER(ArmEnvHerPopArgs), _P]),
+    "armenv_pop_count_episodes": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P]),
+    "armenv_pop_write_episodes": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, _P,
+                                            C.c_int64, _P]),
     "armenv_td3_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
     "armenv_td3_update": (C.c_int, [C.POINTER(ArmEnvTd3Args), _P]),
     "armenv_td3_pop_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),

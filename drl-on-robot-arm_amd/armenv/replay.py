@@ -1,7 +1,9 @@
 """Device-resident trajectory store with the reference's HER-"future" sampling
 (/root/reference/utils/rl_utils.py:91-199: Trajectory, ReplayBuffer_Trajectory_reach / _push), fed directly by the
 [T, N, ...] tensors a rollout produces.  Nothing leaves HBM: episodes are indexed and batches are gathered by HIP
-kernels behind the C ABI (armenv_count_episodes / armenv_write_episodes / armenv_her_sample)."""
+kernels behind the C ABI (armenv_count_episodes / armenv_write_episodes / armenv_her_sample).  ``PopulationTrajectoryStore`` is the
+store of P members trained side by side (armenv.train_pop): P stacked rings of one geometry, indexed and sampled in one launch each
+(armenv_pop_count_episodes / armenv_pop_write_episodes / armenv_her_pop_sample)."""
 import ctypes as C
 
 import torch
@@ -11,6 +13,24 @@ from . import _lib as L
 
 def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def ring_append(cap, base, T, at_reset, Tc):
+    """The ring arithmetic of appending a chunk of ``Tc`` steps to a window of ``T`` logical steps that starts at physical row
+    ``base`` of ``cap`` rows: the oldest steps that no longer fit fall out (the window then starts mid-episode).  Returns
+    (base, T, at_reset, segments) after the append; segments = [(ring row, chunk row, rows)], one entry, or two where the chunk
+    wraps.  The one copy of this arithmetic: TrajectoryStore and PopulationTrajectoryStore both call it."""
+    drop = max(0, T + Tc - cap)                            # oldest steps that fall out of the window
+    if drop:
+        base = (base + drop) % cap
+        T -= drop
+        at_reset = False                                   # the window now starts mid-episode
+    w = (base + T) % cap                                   # physical row of the first new step
+    first = min(Tc, cap - w)
+    segments = [(w, 0, first)]
+    if first < Tc:
+        segments.append((0, first, Tc - first))
+    return base, T + Tc, at_reset, segments
 
 
 class Trajectory:
@@ -71,19 +91,10 @@ class TrajectoryStore:
                 for k, v in src.items():
                     r[k] = torch.empty((cap,) + tuple(v.shape[1:]), dtype=v.dtype, device=self.device)
                 self._ring = r
-            cap = r["cap"]
-            drop = max(0, r["T"] + Tc - cap)                   # oldest steps that fall out of the window
-            if drop:
-                r["base"] = (r["base"] + drop) % cap
-                r["T"] -= drop
-                r["at_reset"] = False                         # the window now starts mid-episode
-            w = (r["base"] + r["T"]) % cap                     # physical row of the first new step
-            first = min(Tc, cap - w)
+            r["base"], r["T"], r["at_reset"], segments = ring_append(r["cap"], r["base"], r["T"], r["at_reset"], Tc)
             for k, v in src.items():
-                r[k][w:w + first].copy_(v[:first])
-                if first < Tc:
-                    r[k][: Tc - first].copy_(v[first:])
-            r["T"] += Tc
+                for row, at, rows in segments:
+                    r[k][row:row + rows].copy_(v[at:at + rows])
         self._index()
 
     def add_trajectory(self, traj):
@@ -173,6 +184,178 @@ class TrajectoryStore:
             out["picks"] = torch.empty((B, 4), dtype=torch.int32, device=dev)
             a.picks_out_dev = out["picks"].data_ptr()
         L.check(self._lib.armenv_her_sample(dev.index or 0, C.byref(a), self._stream()))
+        if pk is not None:
+            torch.cuda.current_stream(dev).synchronize()
+        return out
+
+
+# ring tensor <- the key of the rollout's output dict that feeds it (BatchedEnv.bind_rollout's names)
+_RING_SOURCES = dict(obs_after="obs", next_obs="terminal_obs", action="actions", reward="reward", done="done_u8")
+_BATCH_KEYS = ("states", "actions", "next_states", "rewards", "dones")
+
+
+class PopulationTrajectoryStore:
+    """The trajectory stores of P members that run in lockstep (armenv.train_pop): P rings of one geometry, stacked
+    [P][capacity_steps][N][...], with one episode index [P][capacity_steps * N][3] and one count i64 [P].  The members' rollouts write
+    straight into the store's staging block (``rollout_buffers``); ``add_rollouts`` moves it into the rings and indexes every member,
+    ``sample`` draws every member's batch, each in one launch.  Member p draws with ``seed + p``, and every ``sample`` advances one
+    shared draw counter: member p's ring, index and batches are, bit for bit, those of a ``TrajectoryStore(seed=seed + p)`` that is
+    given member p's rollouts and sampled as often.  Everything is allocated on the first ``add_rollouts``."""
+
+    def __init__(self, members, device="cuda:0", seed=0, capacity_steps=None):
+        if not 1 <= int(members) <= 64:
+            raise ValueError("PopulationTrajectoryStore: members must be 1..64")
+        if capacity_steps is None or int(capacity_steps) < 1:
+            raise ValueError("PopulationTrajectoryStore: capacity_steps (the rows of every member's ring) is required")
+        self.members, self.device, self.seed = int(members), torch.device(device), int(seed)
+        self.capacity = int(capacity_steps)
+        self._lib = L.load()
+        self._draw = 0
+        self._staging = None
+        self._ring = None              # dict(cap, base, T, N, D, at_reset, obs0, the five rings, counts, offsets, episodes, num_episodes)
+        self._bound = None             # (key, out, ArmEnvHerPopArgs) of the last ``sample``
+        self._started = False          # the first add_rollouts has stored obs0
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def rollout_buffers(self, steps, N, D):
+        """P dicts, member p's being contiguous views [steps][N][...] into one stacked staging block [P][steps][N][...], under the
+        keys ``BatchedEnv.bind_rollout`` looks up: pass member p's as ``out=`` and its rollout writes straight into the block."""
+        P, T, dev = self.members, int(steps), self.device
+        f32, u8 = torch.float32, torch.uint8
+        self._staging = dict(obs=torch.zeros((P, T, N, D), dtype=f32, device=dev), reward=torch.zeros((P, T, N), dtype=f32, device=dev),
+                             done_u8=torch.zeros((P, T, N), dtype=u8, device=dev), success_u8=torch.zeros((P, T, N), dtype=u8, device=dev),
+                             actions=torch.zeros((P, T, N, 3), dtype=f32, device=dev),
+                             terminal_obs=torch.zeros((P, T, N, D), dtype=f32, device=dev))
+        return [{k: t[p] for k, t in self._staging.items()} for p in range(P)]
+
+    def _allocate(self, N, D):
+        P, cap, dev = self.members, self.capacity, self.device
+        f32 = torch.float32
+        self._ring = dict(cap=cap, base=0, T=0, N=N, D=D, at_reset=True, obs0=torch.zeros((P, N, D), dtype=f32, device=dev),
+                          obs_after=torch.zeros((P, cap, N, D), dtype=f32, device=dev),
+                          next_obs=torch.zeros((P, cap, N, D), dtype=f32, device=dev),
+                          action=torch.zeros((P, cap, N, 3), dtype=f32, device=dev),
+                          reward=torch.zeros((P, cap, N), dtype=f32, device=dev),
+                          done=torch.zeros((P, cap, N), dtype=torch.uint8, device=dev),
+                          counts=torch.zeros((P, N), dtype=torch.int32, device=dev),
+                          offsets=torch.zeros((P, N), dtype=torch.int64, device=dev),
+                          episodes=torch.zeros((P, cap * N, 3), dtype=torch.int32, device=dev),     # bound: one per step
+                          num_episodes=torch.zeros(P, dtype=torch.int64, device=dev))
+        return self._ring
+
+    def add_rollouts(self, obs0, starts_at_reset=True):
+        """Appends the staging block -- every member's last rollout -- to the rings and indexes every member.  obs0 f32 [P][N][D]:
+        the members' observations before the chunk's first step (read on the first call only: later windows start at rows the ring
+        holds).  ``TrajectoryStore.add_rollout``'s arithmetic, once for all members."""
+        stage = self._staging
+        if stage is None:
+            raise RuntimeError("PopulationTrajectoryStore.add_rollouts: call rollout_buffers(steps, N, D) and roll out into them first")
+        P, Tc, N, D = stage["obs"].shape
+        r = self._ring
+        if r is None:
+            if self.capacity < Tc:
+                raise ValueError("capacity_steps smaller than one rollout chunk")
+            if tuple(obs0.shape) != (P, N, D):
+                raise ValueError("PopulationTrajectoryStore.add_rollouts: obs0 must be [%d][%d][%d]" % (P, N, D))
+            r = self._allocate(N, D)
+        elif (r["N"], r["D"]) != (N, D):
+            raise ValueError("PopulationTrajectoryStore.add_rollouts: the staging block's [N][D] changed")
+        if not self._started:
+            r["obs0"].copy_(obs0)
+            r["at_reset"] = bool(starts_at_reset)
+            self._started = True
+        r["base"], r["T"], r["at_reset"], segments = ring_append(r["cap"], r["base"], r["T"], r["at_reset"], Tc)
+        for k, src in _RING_SOURCES.items():
+            for row, at, rows in segments:
+                r[k][:, row:row + rows].copy_(stage[src][:, at:at + rows])
+        self._index()
+
+    def _index(self):
+        r = self._ring
+        dev, P, stream = self.device.index or 0, self.members, self._stream()
+        geometry = (dev, P, r["T"], r["N"], r["base"], r["cap"], _p(r["done"]), int(r["at_reset"]), _p(r["counts"]))
+        L.check(self._lib.armenv_pop_count_episodes(*geometry, stream))
+        torch.cumsum(r["counts"], 1, dtype=torch.int64, out=r["offsets"])
+        L.check(self._lib.armenv_pop_write_episodes(*geometry, _p(r["offsets"]), _p(r["episodes"]), r["episodes"].shape[1], stream))
+        r["num_episodes"].copy_(r["offsets"][:, -1])
+        self._bound = None                                    # T and base moved
+
+    def sizes(self):
+        """the members' numbers of complete episodes in the window: a list of P ints from one device-to-host transfer"""
+        return [0] * self.members if self._ring is None else self._ring["num_episodes"].tolist()
+
+    def ready(self, minimal_episodes):
+        """armenv.train_pop's lockstep rule: EVERY member holds ``minimal_episodes`` complete episodes (one transfer)"""
+        return min(self.sizes()) >= minimal_episodes
+
+    def member_view(self, p):
+        """member p's ring as the dict ``TrajectoryStore.chunk`` holds: views, no copy"""
+        r = self._ring
+        if r is None:
+            raise RuntimeError("PopulationTrajectoryStore.member_view: no rollout stored")
+        view = {k: r[k] for k in ("cap", "base", "T", "N", "D", "at_reset")}
+        view.update({k: r[k][p] for k in ("obs0", "episodes") + tuple(_RING_SOURCES)})
+        view["num_episodes"] = r["num_episodes"][p:p + 1]
+        return view
+
+    def _bind(self, B, use_her, dis_threshold, her_ratio, out):
+        r, P, D, dev = self._ring, self.members, self._ring["D"], self.device
+        want = dict(states=((P, B, D), torch.float32), actions=((P, B, 3), torch.float32), next_states=((P, B, D), torch.float32),
+                    rewards=((P, B), torch.float32), dones=((P, B), torch.uint8))
+        for k, (shape, dt) in want.items():
+            t = out[k]
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"PopulationTrajectoryStore.sample: out[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {dev}")
+        args = L.ArmEnvHerPopArgs()
+        args.members, args.episodes_stride = P, r["episodes"].shape[1]
+        a = args.one
+        a.T, a.N, a.ring_base, a.ring_cap, a.obs_dim, a.use_her = r["T"], r["N"], r["base"], r["cap"], D, int(bool(use_her))
+        a.obs0_dev, a.obs_after_dev, a.next_obs_dev = r["obs0"].data_ptr(), r["obs_after"].data_ptr(), r["next_obs"].data_ptr()
+        a.action_dev, a.reward_dev, a.done_dev = r["action"].data_ptr(), r["reward"].data_ptr(), r["done"].data_ptr()
+        a.episodes_dev, a.num_episodes_dev = r["episodes"].data_ptr(), r["num_episodes"].data_ptr()
+        a.batch, a.seed = B, self.seed & 0xFFFFFFFFFFFFFFFF
+        a.her_ratio, a.dis_threshold = float(her_ratio), float(dis_threshold)
+        a.states_dev, a.actions_dev, a.next_states_dev = out["states"].data_ptr(), out["actions"].data_ptr(), out["next_states"].data_ptr()
+        a.rewards_dev, a.dones_dev = out["rewards"].data_ptr(), out["dones"].data_ptr()
+        return args
+
+    def sample(self, batch_size, use_her=True, dis_threshold=0.1, her_ratio=0.8, out=None, picks=None, return_picks=False):
+        """Every member's batch in one launch, into ``out``: the stacked dict [P][B][...] of ``FusedPopulation.batch_buffers`` (None:
+        allocated here).  ``picks`` i32 [P][B][4]: teacher-forced draws; ``return_picks``: ``out["picks"]`` i32 [P][B][4] (a tensor of
+        that kind already in ``out`` is written in place).  The argument struct is built once per (``out``, settings,
+        ``add_rollouts``); later calls only refresh `draw` and the two picks pointers."""
+        if self._ring is None:
+            raise RuntimeError("PopulationTrajectoryStore.sample: no rollout stored")
+        P, B, D, dev = self.members, int(batch_size), self._ring["D"], self.device
+        if out is None:
+            out = dict(states=torch.empty((P, B, D), dtype=torch.float32, device=dev),
+                       actions=torch.empty((P, B, 3), dtype=torch.float32, device=dev),
+                       next_states=torch.empty((P, B, D), dtype=torch.float32, device=dev),
+                       rewards=torch.empty((P, B), dtype=torch.float32, device=dev),
+                       dones=torch.empty((P, B), dtype=torch.uint8, device=dev))
+        key = (B, bool(use_her), float(dis_threshold), float(her_ratio)) + tuple(out[k].data_ptr() for k in _BATCH_KEYS)
+        bound = self._bound
+        if bound is not None and bound[0] == key and bound[1] is out:
+            args = bound[2]
+        else:
+            args = self._bind(B, use_her, dis_threshold, her_ratio, out)
+            self._bound = (key, out, args)                    # holds `out`: the pointers in `args` stay valid
+        a = args.one
+        pk = None
+        if picks is not None:
+            pk = torch.as_tensor(picks).to(device=dev, dtype=torch.int32).contiguous()
+            assert tuple(pk.shape) == (P, B, 4)
+        a.picks_dev = None if pk is None else pk.data_ptr()
+        if return_picks:
+            t = out.get("picks")
+            if t is None or tuple(t.shape) != (P, B, 4) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                out["picks"] = torch.empty((P, B, 4), dtype=torch.int32, device=dev)
+        a.picks_out_dev = out["picks"].data_ptr() if return_picks else None
+        a.draw = self._draw
+        self._draw += 1
+        L.check(self._lib.armenv_her_pop_sample(dev.index or 0, C.byref(args), self._stream()))
         if pk is not None:
             torch.cuda.current_stream(dev).synchronize()
         return out

@@ -10,7 +10,11 @@ update is one ``train`` = two reference updates on the batch, as in armenv.train
 
 Member p has its own environments, trajectory store, initial weights and noise, all seeded ``seed + p``.  Rollouts are P launches,
 one per member, each with that member's policy (TD3: its actor; the two-actor agents: their own take_action, fused into the rollout
-kernel); every update samples each member's store into that member's slice of the stacked batch and then runs ONE ``pop.train``.
+kernel).  ``store="population"`` (the default): the members' stores are one armenv.replay.PopulationTrajectoryStore -- the rollouts
+write into its staging block, ONE ``add_rollouts`` per iteration moves them into the stacked rings and indexes every member, and
+every update is ONE ``sample`` of the whole stacked batch and ONE ``pop.train``.  ``store="members"``: P TrajectoryStores, each
+appended to, asked for its size and sampled into that member's slice of the stacked batch on its own -- the same bits, member by
+member, kept for A/B runs (``--store``).
 
 Lockstep rule: the members share the step schedule, so an iteration runs its updates only when EVERY member's store is ready (holds
 ``minimal_episodes`` complete episodes); while one member is not, no member is updated.  The members' stores fill at about the same
@@ -22,49 +26,71 @@ import time
 from .fused_daddpg_pop import FusedDADDPGPopulation
 from .fused_datd3_pop import FusedDARCPopulation, FusedDATD3Population
 from .fused_td3_pop import FusedTD3Population
-from .replay import TrajectoryStore
+from .replay import PopulationTrajectoryStore, TrajectoryStore
 from .train import _TASKS, ALGOS, _install_policy
 
+STORES = ("population", "members")
 _POPULATIONS = dict(td3=FusedTD3Population, daddpg=FusedDADDPGPopulation, datd3=FusedDATD3Population, darc=FusedDARCPopulation)
 
 
 def train_reach_population(members=16, num_envs=64, iterations=200, rollout_steps=32, updates=40, batch_size=256, her_ratio=0.8,
                            seed=0, device="cuda:0", actor_kind="actor_f16x3", expl_sigma=None, log_every=10, log=print,
-                           window_steps=1536, minimal_episodes=5, max_steps=500, task="reach", algo="td3"):
+                           window_steps=1536, minimal_episodes=5, max_steps=500, task="reach", algo="td3", store="population"):
     """Returns (population, history); a history record holds the members' success rates over the last ``log_every`` iterations.
     ``task="push" | "pick"``: armenv.train.train_push's settings (state_dim 9, action_bound 0.4, unclipped exploration noise).
-    ``algo``: the agent; the two-actor agents explore as armenv.train has them explore on that task (the same sigma and clip)."""
+    ``algo``: the agent; the two-actor agents explore as armenv.train has them explore on that task (the same sigma and clip).
+    ``store``: "population" (one PopulationTrajectoryStore) or "members" (P TrajectoryStores); both train the same bits."""
     if task not in _TASKS:
         raise ValueError("task must be one of %s" % ", ".join(_TASKS))
     if algo not in ALGOS:
         raise ValueError("algo must be one of %s" % ", ".join(ALGOS))
+    if store not in STORES:
+        raise ValueError("store must be one of %s" % ", ".join(STORES))
     Env, state_dim, action_bound = _TASKS[task]
     sigma = expl_sigma if expl_sigma is not None else action_bound * 0.98
     noise_clip = action_bound if task == "reach" else 1e9
     P = int(members)
     pop = _POPULATIONS[algo](P, state_dim, 3, action_bound, device=device, seed=seed)
     es = [Env(num_envs, device=device, seed=seed + p, max_steps=max_steps) for p in range(P)]
-    stores = [TrajectoryStore(device=device, seed=seed + p, capacity_steps=window_steps) for p in range(P)]
     batch = pop.batch_buffers(batch_size)
-    slices = [pop.member_buffers(p) for p in range(P)]
     obs = [e.reset() for e in es]
-    bufs = [{} for _ in range(P)]
+    if store == "population":
+        pstore = PopulationTrajectoryStore(P, device=device, seed=seed, capacity_steps=window_steps)
+        bufs = pstore.rollout_buffers(rollout_steps, num_envs, state_dim)
+        obs0 = obs[0].new_empty((P,) + tuple(obs[0].shape))
+    else:
+        stores = [TrajectoryStore(device=device, seed=seed + p, capacity_steps=window_steps) for p in range(P)]
+        slices = [pop.member_buffers(p) for p in range(P)]
+        bufs = [{} for _ in range(P)]
     prev = [e.counters() for e in es]
     history = []
     t0 = time.perf_counter()
     for it in range(iterations):
-        for p, e in enumerate(es):
-            _install_policy(e, algo, pop.member(p), actor_kind, action_bound, sigma, noise_clip)
-            obs0 = obs[p].clone()
-            out = e.rollout(rollout_steps, None, out=bufs[p], want_actions=True, want_terminal_obs=True)
-            obs[p] = out["obs"][-1]
-            stores[p].add_rollout(obs0, out, starts_at_reset=(it == 0))
-        # lockstep: re-checked every iteration (a ring window can lose its complete episodes again, see armenv.train)
-        if all(st.size() >= minimal_episodes for st in stores):
-            for _ in range(updates):
-                for p, st in enumerate(stores):
-                    st.sample(batch_size, use_her=True, her_ratio=her_ratio, out=slices[p])
-                pop.train(batch)                          # datd3 / darc: two updates, as the reference's run() counts them
+        if store == "population":
+            for p, e in enumerate(es):
+                _install_policy(e, algo, pop.member(p), actor_kind, action_bound, sigma, noise_clip)
+                if it == 0:
+                    obs0[p].copy_(obs[p])                  # the window's first observation: read by the first add_rollouts only
+                e.rollout(rollout_steps, None, out=bufs[p], want_actions=True, want_terminal_obs=True)
+            pstore.add_rollouts(obs0, starts_at_reset=(it == 0))
+            # lockstep: re-checked every iteration (a ring window can lose its complete episodes again, see armenv.train)
+            if pstore.ready(minimal_episodes):
+                for _ in range(updates):
+                    pstore.sample(batch_size, use_her=True, her_ratio=her_ratio, out=batch)
+                    pop.train(batch)                      # datd3 / darc: two updates, as the reference's run() counts them
+        else:
+            for p, e in enumerate(es):
+                _install_policy(e, algo, pop.member(p), actor_kind, action_bound, sigma, noise_clip)
+                obs0 = obs[p].clone()
+                out = e.rollout(rollout_steps, None, out=bufs[p], want_actions=True, want_terminal_obs=True)
+                obs[p] = out["obs"][-1]
+                stores[p].add_rollout(obs0, out, starts_at_reset=(it == 0))
+            # lockstep: re-checked every iteration (a ring window can lose its complete episodes again, see armenv.train)
+            if all(st.size() >= minimal_episodes for st in stores):
+                for _ in range(updates):
+                    for p, st in enumerate(stores):
+                        st.sample(batch_size, use_her=True, her_ratio=her_ratio, out=slices[p])
+                    pop.train(batch)                      # datd3 / darc: two updates, as the reference's run() counts them
         if (it + 1) % log_every == 0:
             cs = [e.counters() for e in es]
             rates = [(c["successes"] - c0["successes"]) / max(1, c["episodes"] - c0["episodes"]) for c, c0 in zip(cs, prev)]
@@ -92,9 +118,11 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--window-steps", type=int, default=1536)
     ap.add_argument("--max-steps", type=int, default=500)
+    ap.add_argument("--store", default="population", choices=list(STORES),
+                    help="population: one stacked store, indexed and sampled in one launch each; members: one store per member")
     a = ap.parse_args()
     train_reach_population(a.members, a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed,
-                           actor_kind=a.actor, window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, algo=a.algo)
+                           actor_kind=a.actor, window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, algo=a.algo, store=a.store)
 
 
 if __name__ == "__main__":

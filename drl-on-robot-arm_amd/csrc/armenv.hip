@@ -624,6 +624,22 @@ int armenv_probe_issue_rate(int32_t device, int32_t precision, int32_t waves_per
   return precision == 64 ? issue_probe<double>(device, waves_per_simd, ns_per_instruction) : issue_probe<float>(device, waves_per_simd, ns_per_instruction);
 }
 
+}  // extern "C"
+
+static HerArgs her_args(const ArmEnvHerArgs *a) {
+  HerArgs h;
+  h.T = a->T; h.N = a->N; h.ring_base = a->ring_base; h.ring_cap = a->ring_cap; h.D = a->obs_dim;
+  h.obs0 = a->obs0_dev; h.obs_after = a->obs_after_dev; h.next_obs = a->next_obs_dev; h.action = a->action_dev;
+  h.reward = a->reward_dev; h.done = a->done_dev; h.episodes = a->episodes_dev; h.num_episodes = a->num_episodes_dev;
+  h.B = a->batch; h.picks_in = a->picks_dev; h.seed = a->seed; h.draw = a->draw; h.use_her = a->use_her;
+  h.her_ratio = a->her_ratio; h.dis_threshold = a->dis_threshold;
+  h.states = a->states_dev; h.actions = a->actions_dev; h.next_states = a->next_states_dev; h.rewards = a->rewards_dev;
+  h.dones = a->dones_dev; h.picks_out = a->picks_out_dev;
+  return h;
+}
+
+extern "C" {
+
 int armenv_her_sample(int32_t device, const ArmEnvHerArgs *a, void *stream) {
   DEV_ENTER(device);
   if (!a) return fail(ARMENV_EINVAL, "armenv_her_sample: args is NULL");
@@ -636,20 +652,88 @@ int armenv_her_sample(int32_t device, const ArmEnvHerArgs *a, void *stream) {
     return fail(ARMENV_EINVAL, "armenv_her_sample: NULL buffer");
   if (!(a->her_ratio >= 0.f && a->her_ratio <= 1.f)) return fail(ARMENV_EINVAL, "armenv_her_sample: her_ratio outside [0,1]");
   if (a->batch == 0) return ARMENV_OK;
-  HerArgs h;
-  h.T = a->T; h.N = a->N; h.ring_base = a->ring_base; h.ring_cap = a->ring_cap; h.D = a->obs_dim;
-  h.obs0 = a->obs0_dev; h.obs_after = a->obs_after_dev; h.next_obs = a->next_obs_dev; h.action = a->action_dev;
-  h.reward = a->reward_dev; h.done = a->done_dev; h.episodes = a->episodes_dev; h.num_episodes = a->num_episodes_dev;
-  h.B = a->batch; h.picks_in = a->picks_dev; h.seed = a->seed; h.draw = a->draw; h.use_her = a->use_her;
-  h.her_ratio = a->her_ratio; h.dis_threshold = a->dis_threshold;
-  h.states = a->states_dev; h.actions = a->actions_dev; h.next_states = a->next_states_dev; h.rewards = a->rewards_dev;
-  h.dones = a->dones_dev; h.picks_out = a->picks_out_dev;
+  const HerArgs h = her_args(a);
   const dim3 grid(grid_for(a->batch, 256)), block(256);
   if (a->obs_dim == 6) hipLaunchKernelGGL((her_sample_kernel<6>), grid, block, 0, static_cast<hipStream_t>(stream), h);
   else hipLaunchKernelGGL((her_sample_kernel<9>), grid, block, 0, static_cast<hipStream_t>(stream), h);
   HIP_TRY(hipGetLastError());
   return ARMENV_OK;
 }
+
+// ---- the population forms: every argument is checked before the first HIP call
+#define POP_REFUSE(cond, what) \
+  if (cond) return fail(ARMENV_EINVAL, "%s: %s", __func__, what)
+
+static const char *pop_index_refusal(int32_t members, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap) {
+  if (members < 1 || members > 64) return "members must be 1..64";
+  if (T < 0) return "T must be >= 0";
+  if (N < 1) return "N must be >= 1";
+  if (ring_cap < 1 || ring_cap < T) return "ring_cap must be >= max(T, 1)";
+  if (ring_base < 0) return "ring_base must be >= 0";
+  return nullptr;
+}
+
+int armenv_pop_count_episodes(int32_t device, int32_t members, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap,
+                              const uint8_t *done_dev, int32_t starts_at_reset, int32_t *counts_dev, void *stream) {
+  const char *why = pop_index_refusal(members, T, N, ring_base, ring_cap);
+  POP_REFUSE(why, why);
+  POP_REFUSE(!done_dev, "done_dev is NULL");
+  POP_REFUSE(!counts_dev, "counts_dev is NULL");
+  DEV_ENTER(device);
+  hipLaunchKernelGGL(index_episodes_pop_kernel, dim3(grid_for(N, 256), members), dim3(256), 0, static_cast<hipStream_t>(stream), T, N,
+                     ring_base, ring_cap, done_dev, starts_at_reset, counts_dev, (const int64_t *)nullptr, (int32_t *)nullptr,
+                     members, (int64_t)0);
+  HIP_TRY(hipGetLastError());
+  return ARMENV_OK;
+}
+
+int armenv_pop_write_episodes(int32_t device, int32_t members, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap,
+                              const uint8_t *done_dev, int32_t starts_at_reset, const int32_t *counts_dev,
+                              const int64_t *offsets_dev, int32_t *episodes_dev, int64_t episodes_stride, void *stream) {
+  const char *why = pop_index_refusal(members, T, N, ring_base, ring_cap);
+  POP_REFUSE(why, why);
+  POP_REFUSE(!done_dev, "done_dev is NULL");
+  POP_REFUSE(!counts_dev, "counts_dev is NULL");
+  POP_REFUSE(!offsets_dev, "offsets_dev is NULL");
+  POP_REFUSE(!episodes_dev, "episodes_dev is NULL");
+  POP_REFUSE(episodes_stride < 1, "episodes_stride must be >= 1");
+  DEV_ENTER(device);
+  hipLaunchKernelGGL(index_episodes_pop_kernel, dim3(grid_for(N, 256), members), dim3(256), 0, static_cast<hipStream_t>(stream), T, N,
+                     ring_base, ring_cap, done_dev, starts_at_reset, const_cast<int32_t *>(counts_dev), offsets_dev, episodes_dev,
+                     members, episodes_stride);
+  HIP_TRY(hipGetLastError());
+  return ARMENV_OK;
+}
+
+int armenv_her_pop_sample(int32_t device, const ArmEnvHerPopArgs *args, void *stream) {
+  POP_REFUSE(!args, "args is NULL");
+  const ArmEnvHerArgs *a = &args->one;
+  POP_REFUSE(args->members < 1 || args->members > 64, "members must be 1..64");
+  POP_REFUSE(args->episodes_stride < 1, "episodes_stride must be >= 1");
+  POP_REFUSE(a->obs_dim != 6 && a->obs_dim != 9, "obs_dim must be 6 or 9");
+  POP_REFUSE(a->batch < 0, "batch must be >= 0");
+  POP_REFUSE(a->T < 1, "T must be >= 1");
+  POP_REFUSE(a->N < 1, "N must be >= 1");
+  POP_REFUSE(a->ring_cap < a->T, "ring_cap must be >= T");
+  POP_REFUSE(a->ring_base < 0, "ring_base must be >= 0");
+#define POP_NEEDS(field) POP_REFUSE(!a->field, #field " is NULL")
+  POP_NEEDS(obs0_dev); POP_NEEDS(obs_after_dev); POP_NEEDS(next_obs_dev); POP_NEEDS(action_dev); POP_NEEDS(reward_dev);
+  POP_NEEDS(done_dev); POP_NEEDS(episodes_dev); POP_NEEDS(num_episodes_dev); POP_NEEDS(states_dev); POP_NEEDS(actions_dev);
+  POP_NEEDS(next_states_dev); POP_NEEDS(rewards_dev); POP_NEEDS(dones_dev);
+#undef POP_NEEDS
+  POP_REFUSE(!(a->her_ratio >= 0.f && a->her_ratio <= 1.f), "her_ratio outside [0,1]");
+  if (a->batch == 0) return ARMENV_OK;
+  DEV_ENTER(device);
+  const HerArgs h = her_args(a);
+  const dim3 grid(grid_for(a->batch, 256), args->members), block(256);
+  if (a->obs_dim == 6)
+    hipLaunchKernelGGL((her_sample_pop_kernel<6>), grid, block, 0, static_cast<hipStream_t>(stream), h, args->members, args->episodes_stride);
+  else
+    hipLaunchKernelGGL((her_sample_pop_kernel<9>), grid, block, 0, static_cast<hipStream_t>(stream), h, args->members, args->episodes_stride);
+  HIP_TRY(hipGetLastError());
+  return ARMENV_OK;
+}
+#undef POP_REFUSE
 
 int64_t armenv_num_envs(const ArmEnv *env) { return env ? env->cfg.num_envs : 0; }
 int32_t armenv_obs_dim(const ArmEnv *env) { return env ? (env->cfg.task == ARMENV_TASK_REACH ? 6 : 9) : 0; }

@@ -21,11 +21,8 @@ namespace armenv {
 // pass 1: number of complete episodes per env column; pass 2 (write != nullptr): emit (env, t_start, length).
 // `starts_at_reset`: the chunk began right after a reset of every env, so the first episode's start is inside it.
 // The buffers may be a ring: logical step t lives in physical row (ring_base + t) % ring_cap (ring_cap >= T).
-__global__ __launch_bounds__(256) void index_episodes_kernel(int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap,
-                                                            const uint8_t *done, int32_t starts_at_reset,
-                                                            int32_t *counts, const int64_t *offsets, int32_t *episodes) {
-  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
+AE_DEV void index_episodes_column(int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap, const uint8_t *done,
+                                  int32_t starts_at_reset, int32_t *counts, const int64_t *offsets, int32_t *episodes, int64_t n) {
   int32_t cnt = 0;
   int64_t start = starts_at_reset ? 0 : -1;
   int64_t w = episodes ? (offsets[n] - (int64_t)counts[n]) : 0;   // offsets = inclusive cumsum of counts
@@ -45,6 +42,28 @@ __global__ __launch_bounds__(256) void index_episodes_kernel(int64_t T, int64_t 
   if (!episodes) counts[n] = cnt;
 }
 
+__global__ __launch_bounds__(256) void index_episodes_kernel(int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap,
+                                                            const uint8_t *done, int32_t starts_at_reset,
+                                                            int32_t *counts, const int64_t *offsets, int32_t *episodes) {
+  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  index_episodes_column(T, N, ring_base, ring_cap, done, starts_at_reset, counts, offsets, episodes, n);
+}
+
+// The population form: member blockIdx.y of P rings of one geometry, done u8 [P][ring_cap][N], counts i32 [P][N], offsets i64 [P][N]
+// (the inclusive cumsum WITHIN each member), episodes i32 [P][episodes_stride][3].  One thread per (member, env column); a member's
+// list is what index_episodes_kernel writes for that member's ring alone.
+__global__ __launch_bounds__(256) void index_episodes_pop_kernel(int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap,
+                                                                const uint8_t *done, int32_t starts_at_reset, int32_t *counts,
+                                                                const int64_t *offsets, int32_t *episodes,
+                                                                int32_t members, int64_t episodes_stride) {
+  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t p = blockIdx.y;
+  if (n >= N || p >= members) return;
+  index_episodes_column(T, N, ring_base, ring_cap, done + p * ring_cap * N, starts_at_reset, counts + p * N,
+                        episodes ? offsets + p * N : nullptr, episodes ? episodes + p * episodes_stride * 3 : nullptr, n);
+}
+
 struct HerArgs {
   int64_t T, N, ring_base, ring_cap;
   int32_t D;                 // 6 reach, 9 push
@@ -62,10 +81,9 @@ struct HerArgs {
   int32_t *picks_out;        // nullable
 };
 
+// sample b of the batch: the one body of her_sample_kernel and her_sample_pop_kernel
 template <int D>
-__global__ __launch_bounds__(256) void her_sample_kernel(HerArgs A) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= A.B) return;
+AE_DEV void her_sample_one(const HerArgs &A, int64_t b) {
   const int64_t E = *A.num_episodes;
   int32_t ep, st, her, sg;
   if (A.picks_in) {
@@ -132,6 +150,34 @@ __global__ __launch_bounds__(256) void her_sample_kernel(HerArgs A) {
   A.rewards[b] = r;
   A.dones[b] = dn;
   if (A.picks_out) { A.picks_out[4 * b] = ep; A.picks_out[4 * b + 1] = st; A.picks_out[4 * b + 2] = her; A.picks_out[4 * b + 3] = sg; }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void her_sample_kernel(HerArgs A) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= A.B) return;
+  her_sample_one<D>(A, b);
+}
+
+// The population form: A is member 0's arguments, member p = blockIdx.y reads and writes the same arrays p x (one member's extent)
+// further on (the rings [P][ring_cap][N][...], obs0 [P][N][D], episodes [P][episodes_stride][3], num_episodes [P], the outputs
+// [P][B][...], the picks [P][B][4]) and draws with seed + p and the shared draw: member p's slices hold what her_sample_kernel
+// leaves when it is given member p's arrays.
+template <int D>
+__global__ __launch_bounds__(256) void her_sample_pop_kernel(HerArgs A, int32_t members, int64_t episodes_stride) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t p = blockIdx.y;
+  if (b >= A.B || p >= members) return;
+  const int64_t ring = p * A.ring_cap * A.N, out = p * A.B;
+  A.obs0 += p * A.N * D;
+  A.obs_after += ring * D; A.next_obs += ring * D; A.action += ring * 3; A.reward += ring; A.done += ring;
+  A.episodes += p * episodes_stride * 3;
+  A.num_episodes += p;
+  A.states += out * D; A.next_states += out * D; A.actions += out * 3; A.rewards += out; A.dones += out;
+  if (A.picks_in) A.picks_in += out * 4;
+  if (A.picks_out) A.picks_out += out * 4;
+  A.seed += (uint64_t)p;
+  her_sample_one<D>(A, b);
 }
 
 }  // namespace armenv

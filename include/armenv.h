@@ -42,6 +42,8 @@ extern "C" {
                                      in the same way;
                                      still 8: + armenv_daddpg_pop_update, armenv_datd3_pop_update, their *_pop_workspace_bytes and
                                      ArmEnvDaddpgPopArgs / ArmEnvDatd3PopArgs, additive in the same way;
+                                     still 8: + armenv_her_pop_sample, armenv_pop_count_episodes, armenv_pop_write_episodes and
+                                     ArmEnvHerPopArgs, additive in the same way;
                                   7: + armenv_td3_update, armenv_td3_workspace_bytes, ArmEnvMlpRW, ArmEnvTd3Args;
                                   6: + armenv_set_policy_daddpg, armenv_episode_returns_f32, ARMENV_POLICY_DADDPG; ArmEnvConfig unchanged since 5 */
 
@@ -441,6 +443,39 @@ typedef struct ArmEnvHerArgs {
  * uniform episode, uniform step, with probability her_ratio a future state's first three dims become the goal,
  * reward -0.1 / 1.0 and done by the distance threshold. */
 int armenv_her_sample(int32_t device, const ArmEnvHerArgs *args, void *stream);
+
+/* ---- the trajectory stores of a population of P members (armenv.replay.PopulationTrajectoryStore): P rings of ONE geometry
+ * (T, N, ring_base, ring_cap and starts_at_reset are shared: the members run in lockstep), stacked member-major, indexed and
+ * sampled in one launch each.  Member p's arrays lie p x (one member's extent) behind member 0's:
+ *   obs0 [P][N][D];  obs_after, next_obs [P][ring_cap][N][D];  action [P][ring_cap][N][3];  reward, done [P][ring_cap][N];
+ *   episodes i32 [P][episodes_stride][3];  num_episodes i64 [P];  counts i32 [P][N];  offsets i64 [P][N]
+ *   outputs [P][B][D], [P][B][3], [P][B];  picks in and out [P][B][4].
+ * All three refuse a bad argument with ARMENV_EINVAL, the field named in armenv_last_error(), before any HIP call. */
+
+/* armenv_count_episodes / armenv_write_episodes for every member at once: one thread per (member, env column).
+ * offsets_dev = the inclusive cumsum of counts_dev WITHIN each member (torch.cumsum(counts, 1)); member p's list, E_p =
+ * offsets[p][N-1] rows at episodes_dev + p x episodes_stride x 3, is the list armenv_write_episodes gives for member p's ring
+ * alone (env-major, then time); rows from E_p on are not written.  episodes_stride >= E_p is the caller's to guarantee:
+ * ring_cap x N always suffices (an episode ends on a step). */
+int armenv_pop_count_episodes(int32_t device, int32_t members, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap,
+                              const uint8_t *done_dev, int32_t starts_at_reset, int32_t *counts_dev, void *stream);
+int armenv_pop_write_episodes(int32_t device, int32_t members, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap,
+                              const uint8_t *done_dev, int32_t starts_at_reset, const int32_t *counts_dev,
+                              const int64_t *offsets_dev, int32_t *episodes_dev, int64_t episodes_stride, void *stream);
+
+typedef struct ArmEnvHerPopArgs {
+  ArmEnvHerArgs one;        /* member 0's arrays; member p's at p x (one member's extent), see above;
+                               num_episodes_dev i64 [P]; outputs [P][B][...]; picks [P][B][4]; seed: member p draws with seed + p */
+  int32_t members;          /* P, 1..64 */
+  int64_t episodes_stride;  /* rows of [3] reserved per member in episodes_dev, >= 1 */
+} ArmEnvHerPopArgs;
+
+/* armenv_her_sample for every member in one launch (grid: ceil(B / 256) blocks x P members).  Contract: it leaves in member p's
+ * slices exactly the bytes that armenv_her_sample leaves when it is given member p's arrays, seed + p (uint64 wrap-around) and
+ * the same draw -- a member whose num_episodes is 0 gets that call's inert batch (zeros, done = 1, picks -1, 0, 0, 0).
+ * Refused: NULL args, members outside 1..64, episodes_stride < 1 and everything armenv_her_sample refuses (obs_dim, sizes, NULL
+ * buffers, her_ratio).  batch == 0: ARMENV_OK, nothing is launched. */
+int armenv_her_pop_sample(int32_t device, const ArmEnvHerPopArgs *args, void *stream);
 
 /* ---- fused TD3 learner: one TD3_MLP.train update (the reference's algo/TD3/TD3_mlp.py:114-161) over the networks of
  * net_mlp.py:29-71 (actor: fc1-3, tanh x action_bound; twin critic over cat(s, a): fc1-3 = Q1, fc4-6 = Q2), hidden_dim 256:

@@ -1,0 +1,247 @@
+"""CPU tests of the host side of the population trajectory store (armenv_her_pop_sample, armenv_pop_count_episodes,
+armenv_pop_write_episodes, include/armenv.h; armenv.replay.PopulationTrajectoryStore): the ctypes struct agrees with the header, every
+argument is refused before any HIP call, the population kernels are in the built code object without scratch or LDS, and the stacked
+rings keep TrajectoryStore's books."""
+import ctypes as C
+import os
+import subprocess
+import sys
+import tempfile
+
+import pytest
+import torch
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import isa  # noqa: E402
+
+HEADER_DIR = os.path.join(ROOT, "include")
+EINVAL = -1
+POINTERS = ("obs0_dev", "obs_after_dev", "next_obs_dev", "action_dev", "reward_dev", "done_dev", "episodes_dev", "num_episodes_dev",
+            "states_dev", "actions_dev", "next_states_dev", "rewards_dev", "dones_dev")
+
+
+# ------------------------------------------------------------------------------------------------ H1: ABI layout
+
+def _ctypes_layout(struct, prefix=""):
+    out = []
+    for name, typ in struct._fields_:
+        off = getattr(struct, name).offset
+        if isinstance(typ, type) and issubclass(typ, C.Structure):
+            out += [(f"{prefix}{name}.{k}", off + o) for k, o in _ctypes_layout(typ, "")]
+        else:
+            out.append((prefix + name, off))
+    return out
+
+
+def test_struct_layout_matches_the_header():
+    from armenv import _lib as L
+    members = _ctypes_layout(L.ArmEnvHerPopArgs)
+    assert [m for m, _ in members][-2:] == ["members", "episodes_stride"] and ("one.picks_out_dev", L.ArmEnvHerArgs.picks_out_dev.offset) in members
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "armenv.h"', "int main(void) {",
+             '  printf("%zu %zu\\n", sizeof(ArmEnvHerPopArgs), sizeof(ArmEnvHerArgs));']
+    lines += ['  printf("%%zu\\n", offsetof(ArmEnvHerPopArgs, %s));' % m for m, _ in members]
+    lines += ["  return 0;", "}"]
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
+        with open(src, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        subprocess.run(["gcc", "-std=c99", "-Wall", "-I", HEADER_DIR, "-o", exe, src], check=True)
+        out = subprocess.run([exe], check=True, stdout=subprocess.PIPE, text=True).stdout.split()
+    assert int(out[0]) == C.sizeof(L.ArmEnvHerPopArgs) and int(out[1]) == C.sizeof(L.ArmEnvHerArgs)
+    assert [int(x) for x in out[2:]] == [o for _, o in members], members
+    assert L.ArmEnvHerPopArgs.members.offset == C.sizeof(L.ArmEnvHerArgs)
+
+
+def test_the_symbols_resolve_and_the_abi_version_did_not_move():
+    from armenv import _lib as L
+    lib = L.load()
+    assert lib.armenv_abi_version() == 8 and L.ABI_VERSION == 8
+    for name in ("armenv_her_pop_sample", "armenv_pop_count_episodes", "armenv_pop_write_episodes"):
+        assert name in L.SYMBOLS and getattr(lib, name) is not None
+
+
+# ------------------------------------------------------------------------------------------------ H2: refusals
+
+def _args(P=3, B=64, D=6):
+    """Arguments that pass every check but the one a test breaks: fake (never dereferenced) device pointers.
+    NOT to be passed unmodified -- a valid set would be enqueued."""
+    from armenv import _lib as L
+    pa = L.ArmEnvHerPopArgs()
+    pa.members, pa.episodes_stride = P, 40 * 8
+    a = pa.one
+    a.T, a.N, a.ring_base, a.ring_cap, a.obs_dim, a.use_her, a.batch = 23, 8, 31, 40, D, 1, B
+    a.her_ratio, a.dis_threshold, a.seed, a.draw = 0.8, 0.1, 5, 0
+    for k, name in enumerate(POINTERS):
+        setattr(a, name, 0x10000000 + 0x1000000 * k)
+    return pa
+
+
+def _refused(fn, *args):
+    from armenv import _lib as L
+    lib = L.load()
+    rc, msg = getattr(lib, fn)(*args), lib.armenv_last_error().decode()
+    assert rc == EINVAL, (rc, msg)                       # ARMENV_EINVAL, not ENODEV: nothing touched the device
+    assert msg.startswith(fn), msg
+    return msg
+
+
+def _one(field, value):
+    return lambda pa: setattr(pa.one, field, value)
+
+
+SAMPLE_REFUSALS = [
+    ("members", lambda pa: setattr(pa, "members", 0)),
+    ("members", lambda pa: setattr(pa, "members", 65)),
+    ("members", lambda pa: setattr(pa, "members", -1)),
+    ("episodes_stride", lambda pa: setattr(pa, "episodes_stride", 0)),
+    ("episodes_stride", lambda pa: setattr(pa, "episodes_stride", -3)),
+    ("obs_dim", _one("obs_dim", 7)),
+    ("obs_dim", _one("obs_dim", 0)),
+    ("batch", _one("batch", -1)),
+    ("T", _one("T", 0)),
+    ("N", _one("N", 0)),
+    ("ring_cap", _one("ring_cap", 22)),
+    ("ring_base", _one("ring_base", -1)),
+    ("her_ratio", _one("her_ratio", 1.5)),
+    ("her_ratio", _one("her_ratio", -0.1)),
+    ("her_ratio", _one("her_ratio", float("nan"))),
+] + [(name, _one(name, None)) for name in POINTERS]
+
+
+@pytest.mark.parametrize("field,mutate", SAMPLE_REFUSALS)
+def test_bad_sample_arguments_are_refused_before_any_device_call(field, mutate):
+    pa = _args()
+    mutate(pa)
+    assert field in _refused("armenv_her_pop_sample", 0, C.byref(pa), None)
+
+
+def test_null_sample_args_are_refused():
+    assert "args" in _refused("armenv_her_pop_sample", 0, None, None)
+
+
+@pytest.mark.parametrize("members", [1, 64])
+def test_the_member_bounds_are_accepted(members):
+    """1 and 64 pass the `members` check: the call is then refused for the next broken field, still before any device call; and an
+    empty batch is ARMENV_OK without a launch."""
+    from armenv import _lib as L
+    pa = _args(P=members)
+    pa.one.obs_dim = 7
+    assert "obs_dim" in _refused("armenv_her_pop_sample", 0, C.byref(pa), None)
+    pa = _args(P=members, B=0)
+    assert L.load().armenv_her_pop_sample(0, C.byref(pa), None) == 0
+
+
+GOOD_INDEX = dict(members=3, T=23, N=8, ring_base=31, ring_cap=40, done=0x10000000, counts=0x20000000, offsets=0x30000000,
+                  episodes=0x40000000, stride=320)
+INDEX_REFUSALS = [("members", dict(members=0)), ("members", dict(members=65)), ("T", dict(T=-1)), ("N", dict(N=0)),
+                  ("ring_cap", dict(ring_cap=22)), ("ring_cap", dict(T=0, ring_cap=0)), ("ring_base", dict(ring_base=-1)),
+                  ("done_dev", dict(done=None)), ("counts_dev", dict(counts=None))]
+
+
+@pytest.mark.parametrize("field,change", INDEX_REFUSALS)
+def test_bad_count_arguments_are_refused_before_any_device_call(field, change):
+    g = dict(GOOD_INDEX, **change)
+    assert field in _refused("armenv_pop_count_episodes", 0, g["members"], g["T"], g["N"], g["ring_base"], g["ring_cap"], g["done"], 1,
+                             g["counts"], None)
+
+
+@pytest.mark.parametrize("field,change", INDEX_REFUSALS + [("offsets_dev", dict(offsets=None)), ("episodes_dev", dict(episodes=None)),
+                                                           ("episodes_stride", dict(stride=0))])
+def test_bad_write_arguments_are_refused_before_any_device_call(field, change):
+    g = dict(GOOD_INDEX, **change)
+    assert field in _refused("armenv_pop_write_episodes", 0, g["members"], g["T"], g["N"], g["ring_base"], g["ring_cap"], g["done"], 1,
+                             g["counts"], g["offsets"], g["episodes"], g["stride"], None)
+
+
+# ------------------------------------------------------------------------------------------------ H3: kernels present
+
+@pytest.fixture(scope="module")
+def store_kernels():
+    if not os.path.exists(isa.LIB):
+        pytest.skip("libarmenv.so is not built")
+    if not os.path.exists(os.path.join(isa.LLVM, "llvm-objdump")):
+        pytest.skip("the ROCm LLVM tools (llvm-objdump, llvm-readelf) are not installed")
+    return {dm.replace("void ", "").split("(")[0].replace("armenv::", ""): (md, ins) for _, dm, md, ins in isa.all_kernels()
+            if "her_sample" in dm or "index_episodes" in dm}
+
+
+def test_population_store_kernels_are_in_the_code_object(store_kernels):
+    want = ("her_sample_pop_kernel<6>", "her_sample_pop_kernel<9>", "index_episodes_pop_kernel")
+    assert set(want) <= set(store_kernels), sorted(store_kernels)
+    assert {"her_sample_kernel<6>", "her_sample_kernel<9>", "index_episodes_kernel"} <= set(store_kernels)
+    for k in want:
+        md, ins = store_kernels[k]
+        assert md["scratch"] == 0 and md["lds"] == 0 and md["spill_vgpr"] == 0 and len(ins) > 0, (k, md)
+        mnems = {i.mnem for i in ins}
+        assert not any("atomic" in m or m.startswith(("ds_", "scratch_")) for m in mnems), (k, sorted(mnems))
+
+
+# ------------------------------------------------------------------------------------------------ H4: ring bookkeeping
+
+def test_ring_append_is_the_window_arithmetic():
+    from armenv.replay import ring_append
+    assert ring_append(80, 0, 0, True, 25) == (0, 25, True, [(0, 0, 25)])
+    assert ring_append(80, 0, 75, True, 25) == (20, 80, False, [(75, 0, 5), (0, 5, 20)])
+    assert ring_append(80, 20, 80, False, 25) == (45, 80, False, [(20, 0, 25)])
+    assert ring_append(40, 0, 0, False, 40) == (0, 40, False, [(0, 0, 40)])
+
+
+def test_population_rings_keep_the_single_stores_books(monkeypatch):
+    """Six chunks of 25 steps through cap = 80, on the host (the index launches are left out): after every chunk the population
+    store's base, T and at_reset are TrajectoryStore's, and every member's ring rows are the rows that member's own store holds."""
+    from armenv import replay
+    monkeypatch.setattr(replay.TrajectoryStore, "_index", lambda self: None)
+    monkeypatch.setattr(replay.PopulationTrajectoryStore, "_index", lambda self: None)
+    P, N, D, Tc, cap = 3, 4, 6, 25, 80
+    pop = replay.PopulationTrajectoryStore(P, device="cpu", seed=0, capacity_steps=cap)
+    singles = [replay.TrajectoryStore(device="cpu", seed=p, capacity_steps=cap) for p in range(P)]
+    bufs = pop.rollout_buffers(Tc, N, D)
+    assert all(set(b) == {"obs", "reward", "done_u8", "success_u8", "actions", "terminal_obs"} for b in bufs)
+    assert all(t.is_contiguous() and t.shape[:2] == (Tc, N) for b in bufs for t in b.values())
+    assert bufs[1]["obs"].data_ptr() == pop._staging["obs"][1].data_ptr()
+    gen = torch.Generator().manual_seed(3)
+    obs0 = torch.rand(P, N, D, generator=gen)
+    seen = []
+    for chunk in range(6):
+        for p in range(P):
+            for k, t in bufs[p].items():
+                t.copy_(torch.rand(t.shape, generator=gen) if t.dtype == torch.float32 else (torch.rand(t.shape, generator=gen) < 0.2))
+            singles[p].add_rollout(obs0[p], bufs[p], starts_at_reset=(chunk == 0))
+        pop.add_rollouts(obs0, starts_at_reset=(chunk == 0))
+        r = pop._ring
+        for p, s in enumerate(singles):
+            view = pop.member_view(p)
+            assert (view["cap"], view["base"], view["T"], view["at_reset"], view["N"], view["D"]) == \
+                   (s._ring["cap"], s._ring["base"], s._ring["T"], s._ring["at_reset"], N, D), (chunk, p)
+            rows = [(r["base"] + t) % cap for t in range(r["T"])]
+            for k in ("obs_after", "next_obs", "action", "reward", "done"):
+                assert torch.equal(view[k][rows], s._ring[k][rows]), (chunk, p, k)
+                assert view[k].data_ptr() == r[k][p].data_ptr()
+            assert torch.equal(view["obs0"], s._ring["obs0"])
+        seen.append((r["base"], r["T"], r["at_reset"]))
+    assert seen == [(0, 25, True), (0, 50, True), (0, 75, True), (20, 80, False), (45, 80, False), (70, 80, False)]
+
+
+def test_population_store_refuses_unsupported_construction():
+    from armenv.replay import PopulationTrajectoryStore
+    for kw in (dict(members=0), dict(members=65), dict(members=2, capacity_steps=None)):
+        with pytest.raises(ValueError):
+            PopulationTrajectoryStore(**dict(dict(members=2, device="cpu", capacity_steps=8), **kw))
+    st = PopulationTrajectoryStore(2, device="cpu", capacity_steps=8)
+    assert st.sizes() == [0, 0] and not st.ready(1)
+    with pytest.raises(RuntimeError):
+        st.sample(4)
+    with pytest.raises(RuntimeError):
+        st.add_rollouts(torch.zeros(2, 1, 6))
+    st.rollout_buffers(9, 1, 6)
+    with pytest.raises(ValueError):
+        st.add_rollouts(torch.zeros(2, 1, 6))            # a chunk longer than the ring
+
+
+def test_train_pop_knows_both_stores():
+    from armenv.train_pop import STORES, train_reach_population
+    assert STORES == ("population", "members")
+    with pytest.raises(ValueError):
+        train_reach_population(members=1, iterations=0, store="shared")
