@@ -128,6 +128,11 @@ class ArmEnvDatd3PopArgs(C.Structure):
     _fields_ = [("one", ArmEnvDatd3Args), ("members", C.c_int32)]
 
 
+class ArmEnvPopHyper(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("gamma", "tau", "policy_noise", "noise_clip", "actor_lr", "critic_lr", "q_weight",
+                                         "regularization_weight")]
+
+
 # every symbol include/armenv.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -173,6 +178,9 @@ SYMBOLS = {
     "armenv_daddpg_pop_update": (C.c_int, [C.POINTER(ArmEnvDaddpgPopArgs), _P]),
     "armenv_datd3_pop_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     "armenv_datd3_pop_update": (C.c_int, [C.POINTER(ArmEnvDatd3PopArgs), _P]),
+    "armenv_td3_pop_update_hyper": (C.c_int, [C.POINTER(ArmEnvTd3PopArgs), C.POINTER(ArmEnvPopHyper), _P]),
+    "armenv_daddpg_pop_update_hyper": (C.c_int, [C.POINTER(ArmEnvDaddpgPopArgs), C.POINTER(ArmEnvPopHyper), _P]),
+    "armenv_datd3_pop_update_hyper": (C.c_int, [C.POINTER(ArmEnvDatd3PopArgs), C.POINTER(ArmEnvPopHyper), _P]),
     "armenv_probe_issue_rate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "armenv_probe_clock": (C.c_int, [C.c_int32, _P, C.POINTER(C.c_int32), _P]),
     "armenv_num_envs": (C.c_int64, [_P]),

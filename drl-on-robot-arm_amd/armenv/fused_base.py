@@ -67,12 +67,14 @@ class FusedLearner:
         a = self._Args()
         a.device = self.device.index if self.device.index is not None else torch.cuda.current_device()
         a.state_dim, a.action_dim, a.hidden_dim = self.state_dim, self.action_dim, self.hidden_dim
-        a.action_bound, a.gamma, a.tau = self.action_bound, self.gamma, self.tau
-        a.actor_lr, a.critic_lr = self.actor_lr, self.critic_lr
-        a.beta1, a.beta2, a.eps = self.betas[0], self.betas[1], self.eps
-        for name in self._hyper:
-            setattr(a, name, getattr(self, name))
+        a.action_bound, a.beta1, a.beta2, a.eps = self.action_bound, self.betas[0], self.betas[1], self.eps
+        for name in ("gamma", "tau", "actor_lr", "critic_lr") + self._hyper:
+            setattr(a, name, self._hp(name))
         return a
+
+    def _hp(self, name):
+        """the value of hyper-parameter `name` that the argument struct carries; a population with members' own values: member 0's"""
+        return getattr(self, name)
 
     def batch_buffers(self, batch_size):
         """static input tensors of `batch_size` rows that ``TrajectoryStore.sample(out=...)`` fills in place"""
@@ -142,8 +144,12 @@ class FusedLearner:
         one.states_dev, one.actions_dev, one.next_states_dev = s.data_ptr(), a.data_ptr(), s2.data_ptr()
         one.rewards_dev, one.dones_dev, one.loss_dev = r.data_ptr(), d.data_ptr(), loss.data_ptr()
         one.workspace_dev, one.workspace_bytes = ws.data_ptr(), ws.numel()
-        L.check(self._update_fn(C.byref(self._args), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        L.check(self._enqueue(C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         return loss
+
+    def _enqueue(self, stream):
+        """the one call into libarmenv.so over the bound argument struct; returns its code"""
+        return self._update_fn(C.byref(self._args), stream)
 
     @torch.no_grad()
     def _load_from(self, learner, names):

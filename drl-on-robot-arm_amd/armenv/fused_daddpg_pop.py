@@ -3,9 +3,11 @@
 update, each over P times the workgroups.  At the reference's batch of 256 one learner leaves the device nearly idle; a seed sweep of
 P learners costs about what one does.
 
-Members share the hyper-parameters and the step schedule (total_it, so which actor is stepped, and the three Adam step numbers) and
-nothing else.  Every parameter, target and Adam-moment tensor is member 0's slice of a stack [P][rows][cols] that this object owns;
-member p's update equals, bit for bit, FusedDADDPG's on the same state."""
+Members share the step schedule (total_it, so which actor is stepped, and the three Adam step numbers) and, unless given their own,
+the hyper-parameters: ``actor_lr``, ``critic_lr``, ``tau`` and ``gamma`` each take one value or a sequence of P (fused_pop_base;
+armenv_daddpg_pop_update_hyper then runs the update).  Every parameter, target and Adam-moment tensor is member 0's slice of a stack
+[P][rows][cols] that this object owns; member p's update equals, bit for bit, FusedDADDPG's with member p's hyper-parameters on the
+same state."""
 from . import _lib as L
 from .fused_daddpg import DADDPGSchedule, FusedDADDPG
 from .fused_pop_base import FusedPopulation, TwoActorMember
@@ -15,7 +17,7 @@ _LEARNING = ("actor1", "actor2", "critic")
 
 
 class FusedDADDPGPopulation(DADDPGSchedule, FusedPopulation):
-    """``members`` DADDPG agents with FusedDADDPG's hyper-parameters.  Member p starts from the weights that
+    """``members`` DADDPG agents with FusedDADDPG's hyper-parameters, each one value or P values.  Member p starts from the weights that
     ``torch.manual_seed(seed + p); FusedDADDPG(...)`` creates; the constructor leaves the global random generators as it found them."""
 
     _fn, _PopArgs, _Single = "daddpg_pop", L.ArmEnvDaddpgPopArgs, FusedDADDPG
@@ -24,8 +26,8 @@ class FusedDADDPGPopulation(DADDPGSchedule, FusedPopulation):
 
     def __init__(self, members, state_dim, action_dim, action_bound, hidden_dim=256, actor_lr=1e-3, critic_lr=1e-3, tau=0.005,
                  gamma=0.98, device="cuda:0", seed=0):
-        self._configure(state_dim, action_dim, action_bound, hidden_dim=hidden_dim, actor_lr=actor_lr, critic_lr=critic_lr, tau=tau,
-                        gamma=gamma)
+        self._configure_members(members, state_dim, action_dim, action_bound, hidden_dim=hidden_dim, actor_lr=actor_lr,
+                                critic_lr=critic_lr, tau=tau, gamma=gamma)
         self._create(members, seed, device)
 
     def _member_of(self, p, agent):

@@ -2,12 +2,41 @@
 fused_datd3_pop.FusedDATD3Population / FusedDARCPopulation) share: the stacks [P][rows][cols] that hold every member's nets and Adam
 moments and the re-pointing of the members' module parameters into them, the stacked batch buffers, the checks of a stacked batch,
 what differs in FusedLearner's one call into libarmenv.so (armenv_<algo>_pop_update) and the member-state zip behind load_member /
-export_member.  The step schedule is the agent's own, shared with its single learner (fused_td3.TD3Schedule, ...)."""
+export_member.  The step schedule is the agent's own, shared with its single learner (fused_td3.TD3Schedule, ...).
+
+Per-member hyper-parameters: every constructor takes, for each of its agent's ``sweepable()`` names (the learning rates, tau, gamma,
+the target-policy noise's two, DARC's two weights), a scalar for all members or a sequence of P values; ``hyper(p)`` / ``set_hyper(p,
+...)`` read and change one member's, ``copy_member`` is the exploit step of a population-based schedule.  While every member holds
+the same values the update is armenv_<algo>_pop_update, as before; once two members differ it is armenv_<algo>_pop_update_hyper,
+which hands each member's values to the kernels.  Members always share the step schedule (so ``policy_freq``), Adam's constants,
+``action_bound`` and the shapes."""
+import ctypes as C
+
 import torch
 
+from . import _lib as L
 from .fused_base import FusedLearner, _mlp_of
 
 MAX_MEMBERS = 64
+_NOT_SWEEPABLE = ("hidden_dim", "policy_freq")          # a shape, and the step schedule: the members' one
+_UNIT_RANGE = ("gamma", "tau", "q_weight")              # in [0, 1]; every other sweepable value: >= 0 (the C entry points' ranges)
+
+
+def _check_range(who, name, value):
+    """The C entry points' range of hyper-parameter `name`, checked where the value is given: ``train`` moves its counters before
+    the call, so a value that the call would refuse must not get that far."""
+    if not (0.0 <= value <= 1.0 if name in _UNIT_RANGE else 0.0 <= value < float("inf")):      # NaN fails both
+        raise ValueError("%s: %s = %r out of range" % (who, name, value))
+
+
+def _values(value):
+    """the list of a sequence's values, or None for a scalar"""
+    if isinstance(value, (str, bytes)) or not hasattr(value, "__len__"):
+        return None
+    try:
+        return [float(v) for v in value]
+    except TypeError:                                   # a 0-dim array or tensor
+        return None
 
 
 class TwoActorMember:
@@ -48,6 +77,98 @@ class FusedPopulation(FusedLearner):
     _Single = _PopArgs = None
     _NETS = _MOMENTS = ()
     _batch_axis = 1
+    always_hyper = False        # take armenv_<algo>_pop_update_hyper even while the members' values coincide (tests, A/B timing)
+
+    @classmethod
+    def sweepable(cls):
+        """the hyper-parameters that every member may have a value of its own of"""
+        return tuple(n for n in cls._HYPER_KW if n not in _NOT_SWEEPABLE)
+
+    def _configure_members(self, members, state_dim, action_dim, action_bound, **hyper):
+        """``_configure`` for a population: each of `hyper` a scalar, or -- a sweepable name only -- a sequence of `members` values.
+        An attribute of this object is the members' common value, as a scalar population's always was, or the tuple of their values."""
+        who = type(self).__name__
+        if not 1 <= int(members) <= MAX_MEMBERS:
+            raise ValueError("%s: members must be 1..%d" % (who, MAX_MEMBERS))
+        P, rows, first = int(members), {}, {}
+        for name, value in hyper.items():
+            values = _values(value)
+            if values is None:
+                values = [value] * P
+            elif name not in self.sweepable():
+                raise ValueError("%s: %s takes one value for all members" % (who, name))
+            elif len(values) != P:
+                raise ValueError("%s: %s has %d values for %d members" % (who, name, len(values), P))
+            else:
+                for v in values:
+                    _check_range(who, name, v)
+            first[name] = values[0]
+            if name in self.sweepable():
+                rows[name] = values
+        self._configure(state_dim, action_dim, action_bound, **first)
+        self._rows = [{name: values[p] for name, values in rows.items()} for p in range(P)]
+        self._hyper_changed()
+
+    def _hyper_changed(self):
+        """after a change of the members' values: the attributes, and the call is bound anew"""
+        for name in self._rows[0]:
+            values = [row[name] for row in self._rows]
+            setattr(self, name, values[0] if all(v == values[0] for v in values) else tuple(values))
+        self._args = self._one = self._table = None
+
+    def _hp(self, name):
+        return self._rows[0][name] if name in self._rows[0] else getattr(self, name)
+
+    def uniform(self):
+        """whether all members hold the same hyper-parameters (then the update is the shared-scalar armenv_<algo>_pop_update)"""
+        return all(row == self._rows[0] for row in self._rows)
+
+    @property
+    def entry_point(self):
+        """the name of the C entry point that the next ``train`` calls"""
+        return "armenv_%s_update%s" % (self._fn, "_hyper" if self.always_hyper or not self.uniform() else "")
+
+    def hyper(self, p):
+        """member p's hyper-parameters: a dict over ``sweepable()``"""
+        return dict(self._rows[p])
+
+    def set_hyper(self, p, **values):
+        """Gives member p new values of sweepable hyper-parameters; in effect from the next ``train``.  A captured graph keeps the
+        values it was captured with."""
+        for name in values:
+            if name not in self.sweepable():
+                raise ValueError("%s.set_hyper: %s is not one of %s" % (type(self).__name__, name, ", ".join(self.sweepable())))
+            _check_range(type(self).__name__ + ".set_hyper", name, float(values[name]))
+        row = self._rows[range(self.members)[p]]
+        row.update({name: float(v) for name, v in values.items()})
+        self._hyper_changed()
+
+    @torch.no_grad()
+    def copy_member(self, src, dst, hyper=False):
+        """Member `dst` becomes a copy of member `src`: nets, targets and Adam moments -- and, with `hyper`, its hyper-parameters.
+        The exploit step of population-based training; follow it with ``set_hyper(dst, ...)`` to explore."""
+        src, dst = range(self.members)[src], range(self.members)[dst]
+        for six in self.stacks.values():
+            for t in six:
+                t[dst].copy_(t[src])
+        if hyper:
+            self._rows[dst] = dict(self._rows[src])
+            self._hyper_changed()
+
+    def _bind(self, args):
+        super()._bind(args)
+        self._table = None
+        if self.always_hyper or not self.uniform():
+            self._table = (L.ArmEnvPopHyper * self.members)()
+            for row, h in zip(self._rows, self._table):
+                for name, _ in L.ArmEnvPopHyper._fields_:
+                    setattr(h, name, row[name] if name in row else getattr(self, name, 0.0))   # not the agent's: never read
+        self._bound_fn = getattr(L.load(), self.entry_point)
+
+    def _enqueue(self, stream):
+        if self._table is None:
+            return self._bound_fn(C.byref(self._args), stream)
+        return self._bound_fn(C.byref(self._args), self._table, stream)
 
     def _create(self, members, seed, device):
         """Creates the stacks and the members: member p from the nets of ``torch.manual_seed(seed + p); _single("cpu", seed + p)``.
@@ -62,7 +183,7 @@ class FusedPopulation(FusedLearner):
         with torch.random.fork_rng(devices=list(cuda)):
             for p in range(self.members):
                 torch.manual_seed(self.seed + p)
-                agents.append(self._single("cpu", self.seed + p))
+                agents.append(self._single("cpu", self.seed + p, p))
         # stacks[name]: six tensors [P][rows][cols] (W1, b1, W2, b2, W3, b3) of net or moment `name`
         self.stacks = {}
         for name, six in zip(self._NETS, self._sixes(agents[0])):
@@ -140,9 +261,9 @@ class FusedPopulation(FusedLearner):
         nets = [t for six in cls._sixes(agent) for t in six]
         return nets + [t for m, _ in cls._MOMENTS for t in getattr(agent, m)]
 
-    def _single(self, device, seed):
-        """a single learner with this population's hyper-parameters, and `seed` where the agent takes one"""
-        kw = {name: getattr(self, name) for name in self._HYPER_KW}
+    def _single(self, device, seed, p):
+        """a single learner with member p's hyper-parameters, and `seed` where the agent takes one"""
+        kw = {name: self._rows[p][name] if name in self._rows[p] else getattr(self, name) for name in self._HYPER_KW}
         if self._takes_seed:
             kw["seed"] = seed
         return self._Single(self.state_dim, self.action_dim, self.action_bound, device=device, **kw)
@@ -150,7 +271,8 @@ class FusedPopulation(FusedLearner):
     @torch.no_grad()
     def load_member(self, p, agent):
         """Copies a single learner's whole state into member p: parameters, targets, moments -- and its counters (total_it and the
-        Adam step numbers), which are the population's: load every member from learners at the same step."""
+        Adam step numbers), which are the population's: load every member from learners at the same step.  The member keeps its
+        hyper-parameters."""
         for mine, theirs in zip(self._member_state(p), self._single_state(agent)):
             mine.copy_(theirs)
         for name in self._COUNTERS:
@@ -158,9 +280,11 @@ class FusedPopulation(FusedLearner):
 
     @torch.no_grad()
     def export_member(self, p):
-        """a single learner on this device holding member p's whole state, counters and noise seed (``seed + p``) included"""
+        """a single learner on this device with member p's hyper-parameters, holding member p's whole state, counters and noise seed
+        (``seed + p``) included: its ``train`` on member p's batch does what the population's does to member p"""
+        p = range(self.members)[p]
         with torch.random.fork_rng(devices=[]):         # its initial weights are overwritten: leave the generator alone
-            agent = self._single(self.device, self.seed + p)
+            agent = self._single(self.device, self.seed + p, p)
         for theirs, mine in zip(self._single_state(agent), self._member_state(p)):
             theirs.copy_(mine)
         for name in self._COUNTERS:

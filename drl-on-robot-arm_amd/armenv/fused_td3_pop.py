@@ -3,9 +3,11 @@ csrc/armenv_learner_kernels.inc): as many kernel launches as one FusedTD3 update
 P times the workgroups.  At the reference's batch of 256 one learner leaves the device nearly idle; a seed sweep of P learners costs
 about what one does.
 
-Members share the hyper-parameters and the step schedule (total_it, the Adam step numbers, policy_freq) and nothing else.  Every
-parameter, target and Adam-moment tensor is member 0's slice of a stack [P][rows][cols] that this object owns; member p's update
-equals, bit for bit, FusedTD3's on the same state with seed ``seed + p``."""
+Members share the step schedule (total_it, the Adam step numbers, policy_freq) and, unless given their own, the hyper-parameters:
+``actor_lr``, ``critic_lr``, ``tau``, ``gamma``, ``policy_noise`` and ``noise_clip`` each take one value or a sequence of P
+(fused_pop_base; armenv_td3_pop_update_hyper then runs the update).  Every parameter, target and Adam-moment tensor is member 0's
+slice of a stack [P][rows][cols] that this object owns; member p's update equals, bit for bit, FusedTD3's with member p's
+hyper-parameters on the same state with seed ``seed + p``."""
 from . import _lib as L
 from .fused_pop_base import MAX_MEMBERS, FusedPopulation  # noqa: F401  (MAX_MEMBERS: importable from here as before)
 from .fused_td3 import FusedTD3, TD3Schedule
@@ -32,7 +34,7 @@ class Member:
 
 
 class FusedTD3Population(TD3Schedule, FusedPopulation):
-    """``members`` TD3 agents with FusedTD3's hyper-parameters.  Member p starts from the weights that
+    """``members`` TD3 agents with FusedTD3's hyper-parameters, each one value or P values.  Member p starts from the weights that
     ``torch.manual_seed(seed + p); FusedTD3(...)`` creates and draws its target-policy noise with seed ``seed + p``; the constructor
     leaves the global random generators as it found them."""
 
@@ -42,8 +44,9 @@ class FusedTD3Population(TD3Schedule, FusedPopulation):
 
     def __init__(self, members, state_dim, action_dim, action_bound, hidden_dim=256, actor_lr=1e-3, critic_lr=1e-3, tau=0.005,
                  gamma=0.98, policy_noise=0.2, noise_clip=0.5, policy_freq=3, device="cuda:0", seed=0):
-        self._configure(state_dim, action_dim, action_bound, hidden_dim=hidden_dim, actor_lr=actor_lr, critic_lr=critic_lr, tau=tau,
-                        gamma=gamma, policy_noise=policy_noise, noise_clip=noise_clip, policy_freq=policy_freq)
+        self._configure_members(members, state_dim, action_dim, action_bound, hidden_dim=hidden_dim, actor_lr=actor_lr,
+                                critic_lr=critic_lr, tau=tau, gamma=gamma, policy_noise=policy_noise, noise_clip=noise_clip,
+                                policy_freq=policy_freq)
         self._create(members, seed, device)
 
     @staticmethod

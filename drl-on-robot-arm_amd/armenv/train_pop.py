@@ -7,6 +7,11 @@ update is one ``train`` = two reference updates on the batch, as in armenv.train
 
     python -m armenv.train_pop --members 16 --iterations 200
     python -m armenv.train_pop --members 16 --iterations 200 --algo daddpg
+    python -m armenv.train_pop --members 4 --sweep actor_lr=1e-3,5e-4,2e-4,1e-4 --sweep tau=0.005,0.005,0.01,0.01
+
+``sweep`` (``--sweep NAME=v0,v1,...``, one value per member): the members' own values of the agent's sweepable hyper-parameters
+(``sweepable_names(algo)``: the learning rates, tau, gamma, the target-policy noise's two, DARC's two weights) and of ``expl_sigma``,
+the rollout's exploration sigma -- a hyper-parameter sweep at the price of one run; every history record then carries them.
 
 Member p has its own environments, trajectory store, initial weights and noise, all seeded ``seed + p``.  Rollouts are P launches,
 one per member, each with that member's policy (TD3: its actor; the two-actor agents: their own take_action, fused into the rollout
@@ -33,13 +38,34 @@ STORES = ("population", "members")
 _POPULATIONS = dict(td3=FusedTD3Population, daddpg=FusedDADDPGPopulation, datd3=FusedDATD3Population, darc=FusedDARCPopulation)
 
 
+def sweepable_names(algo):
+    """the names that ``sweep`` may hold for agent `algo`"""
+    return _POPULATIONS[algo].sweepable() + ("expl_sigma",)
+
+
+def _checked_sweep(sweep, algo, members):
+    """`sweep` as {name: [float] * members}; an unknown name or a wrong count raises ValueError"""
+    out = {}
+    for name, values in (sweep or {}).items():
+        if name not in sweepable_names(algo):
+            raise ValueError("sweep: %s is not one of %s's %s" % (name, algo, ", ".join(sweepable_names(algo))))
+        values = [float(v) for v in values]
+        if len(values) != members:
+            raise ValueError("sweep: %s has %d values for %d members" % (name, len(values), members))
+        out[name] = values
+    return out
+
+
 def train_reach_population(members=16, num_envs=64, iterations=200, rollout_steps=32, updates=40, batch_size=256, her_ratio=0.8,
                            seed=0, device="cuda:0", actor_kind="actor_f16x3", expl_sigma=None, log_every=10, log=print,
-                           window_steps=1536, minimal_episodes=5, max_steps=500, task="reach", algo="td3", store="population"):
+                           window_steps=1536, minimal_episodes=5, max_steps=500, task="reach", algo="td3", store="population",
+                           sweep=None):
     """Returns (population, history); a history record holds the members' success rates over the last ``log_every`` iterations.
     ``task="push" | "pick"``: armenv.train.train_push's settings (state_dim 9, action_bound 0.4, unclipped exploration noise).
     ``algo``: the agent; the two-actor agents explore as armenv.train has them explore on that task (the same sigma and clip).
-    ``store``: "population" (one PopulationTrajectoryStore) or "members" (P TrajectoryStores); both train the same bits."""
+    ``store``: "population" (one PopulationTrajectoryStore) or "members" (P TrajectoryStores); both train the same bits.
+    ``sweep``: a dict from a name of ``sweepable_names(algo)`` to one value per member; every record then holds it as ``hyper``.
+    Without it the members share every hyper-parameter and the records and the trained bits are what they always were."""
     if task not in _TASKS:
         raise ValueError("task must be one of %s" % ", ".join(_TASKS))
     if algo not in ALGOS:
@@ -50,7 +76,10 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
     sigma = expl_sigma if expl_sigma is not None else action_bound * 0.98
     noise_clip = action_bound if task == "reach" else 1e9
     P = int(members)
-    pop = _POPULATIONS[algo](P, state_dim, 3, action_bound, device=device, seed=seed)
+    sweep = _checked_sweep(sweep, algo, P)
+    sigmas = sweep.get("expl_sigma", [sigma] * P)
+    pop = _POPULATIONS[algo](P, state_dim, 3, action_bound, device=device, seed=seed,
+                             **{name: values for name, values in sweep.items() if name != "expl_sigma"})
     es = [Env(num_envs, device=device, seed=seed + p, max_steps=max_steps) for p in range(P)]
     batch = pop.batch_buffers(batch_size)
     obs = [e.reset() for e in es]
@@ -68,7 +97,7 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
     for it in range(iterations):
         if store == "population":
             for p, e in enumerate(es):
-                _install_policy(e, algo, pop.member(p), actor_kind, action_bound, sigma, noise_clip)
+                _install_policy(e, algo, pop.member(p), actor_kind, action_bound, sigmas[p], noise_clip)
                 if it == 0:
                     obs0[p].copy_(obs[p])                  # the window's first observation: read by the first add_rollouts only
                 e.rollout(rollout_steps, None, out=bufs[p], want_actions=True, want_terminal_obs=True)
@@ -80,7 +109,7 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
                     pop.train(batch)                      # datd3 / darc: two updates, as the reference's run() counts them
         else:
             for p, e in enumerate(es):
-                _install_policy(e, algo, pop.member(p), actor_kind, action_bound, sigma, noise_clip)
+                _install_policy(e, algo, pop.member(p), actor_kind, action_bound, sigmas[p], noise_clip)
                 obs0 = obs[p].clone()
                 out = e.rollout(rollout_steps, None, out=bufs[p], want_actions=True, want_terminal_obs=True)
                 obs[p] = out["obs"][-1]
@@ -97,6 +126,8 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
             prev = cs
             rec = dict(iteration=it + 1, env_steps=sum(c["env_steps"] for c in cs), episodes=[c["episodes"] for c in cs],
                        success_rate=rates, wall_s=time.perf_counter() - t0)
+            if sweep:
+                rec["hyper"] = sweep
             history.append(rec)
             log(json.dumps(rec))
     for e in es:
@@ -120,9 +151,23 @@ def main():
     ap.add_argument("--max-steps", type=int, default=500)
     ap.add_argument("--store", default="population", choices=list(STORES),
                     help="population: one stacked store, indexed and sampled in one launch each; members: one store per member")
+    ap.add_argument("--sweep", action="append", default=[], metavar="NAME=v0,v1,...",
+                    help="the members' own values of a hyper-parameter (or of expl_sigma), exactly --members of them; repeatable")
     a = ap.parse_args()
+    sweep = {}
+    for item in a.sweep:
+        name, _, values = item.partition("=")
+        try:
+            sweep[name] = [float(v) for v in values.split(",")]
+        except ValueError:
+            ap.error("--sweep %s: NAME=v0,v1,... with numbers" % item)
+    try:
+        sweep = _checked_sweep(sweep, a.algo, a.members)
+    except ValueError as e:
+        ap.error(str(e))
     train_reach_population(a.members, a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed,
-                           actor_kind=a.actor, window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, algo=a.algo, store=a.store)
+                           actor_kind=a.actor, window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, algo=a.algo, store=a.store,
+                           sweep=sweep or None)
 
 
 if __name__ == "__main__":

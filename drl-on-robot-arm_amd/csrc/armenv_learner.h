@@ -24,9 +24,11 @@
 // the mixed target and the pull towards the other critic).
 // No kernel uses atomics, scratch or a memset; nothing is allocated: all intermediates live in the caller's workspace.
 // All nine kernels -- gemm, actor_back, adam and the three updates' actor and critic heads -- are written in
-// armenv_learner_kernels.inc, which the end of this header includes twice: as the single-learner kernels named above and as the
+// armenv_learner_kernels.inc, which the end of this header includes three times: as the single-learner kernels named above, as the
 // *_pop_kernel forms of armenv_td3_pop_update, armenv_daddpg_pop_update and armenv_datd3_pop_update, where a second grid dimension is
-// the member of a population of stacked learners.  This header holds their argument structs and the per-row pieces they are built from.
+// the member of a population of stacked learners, and as the *_pop_hyper_kernel forms of the armenv_*_pop_update_hyper entry points,
+// where adam and the heads that read a hyper-parameter take it from a per-member table.  This header holds their argument structs and
+// the per-row pieces they are built from.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -304,10 +306,20 @@ struct ActorBackStride {
   int64_t ws, Wq1, W3;
 };
 
+// One scalar of the *_pop_hyper_kernel forms (armenv_*_pop_update_hyper): v[p] is member p's value.  A by-value kernel argument
+// beside the strides, filled by the host from the call's ArmEnvPopHyper array; a kernel reads v[blockIdx.y].
+constexpr int LRN_MAX_MEMBERS = 64;
+struct MemberTable {
+  float v[LRN_MAX_MEMBERS];
+};
+
 #define LRN_POP 0
 #include "armenv_learner_kernels.inc"
 #undef LRN_POP
 #define LRN_POP 1
+#include "armenv_learner_kernels.inc"
+#undef LRN_POP
+#define LRN_POP 2
 #include "armenv_learner_kernels.inc"
 #undef LRN_POP
 

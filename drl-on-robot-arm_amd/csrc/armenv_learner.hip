@@ -39,6 +39,11 @@
 // armenv_td3_pop_update, armenv_daddpg_pop_update, armenv_datd3_pop_update and their *_pop_workspace_bytes: the same column for P
 // stacked learners.  The same launches with the *_pop_kernel forms over (workgroups of one member, P); member p's operands lie p
 // member strides behind member 0's (MemberStrides).
+//
+// armenv_td3_pop_update_hyper, armenv_daddpg_pop_update_hyper and armenv_datd3_pop_update_hyper: the population column once more, with
+// a HOST array ArmEnvPopHyper[P] of the members' own hyper-parameters (MemberStrides.hyper).  Stages 3, 6, 9 and 16 -- the only ones
+// whose kernels read such a scalar -- launch their *_pop_hyper_kernel forms with the members' values as MemberTable arguments, each
+// derived scalar formed per member by the single path's expression; every other launch is the population's.
 #include <cmath>
 #include <initializer_list>
 
@@ -114,6 +119,17 @@ struct MemberStrides {
   int n = 0;
   int members = 1;
   int64_t ws = 0;              // the workspace's stride: floats of one single-learner workspace
+  const ArmEnvPopHyper *hyper = nullptr;   // set (host, [members]): armenv_*_pop_update_hyper, the members' own hyper-parameters
+  // member p's value of a scalar: f(hyper[p]), p < members
+  template <class F>
+  MemberTable table(F f) const {
+    MemberTable t{};
+    for (int p = 0; p < members; ++p) t.v[p] = f(hyper[p]);
+    return t;
+  }
+  MemberTable table(float ArmEnvPopHyper::*field) const {
+    return table([field](const ArmEnvPopHyper &h) { return h.*field; });
+  }
   void add(const void *p, int64_t elems, int64_t elem_bytes = sizeof(float)) {
     if (p) arrays[n++] = Array{(uintptr_t)p, (uintptr_t)p + (uintptr_t)(elems * elem_bytes), elems};
   }
@@ -213,15 +229,41 @@ void adam_tensors(AdamArgs &P, const ArmEnvMlpRW &p, const ArmEnvMlpRW &m, const
   }
 }
 
-// Args: ArmEnvTd3Args, ArmEnvDaddpgArgs or ArmEnvDatd3Args (beta1, beta2, eps, tau)
+// A kernel's argument block: its by-value arguments laid out in order, each at its own alignment.
+template <class... KArgs>
+constexpr size_t kernarg_bytes() {
+  size_t o = 0;
+  ((o = (o + alignof(KArgs) - 1) / alignof(KArgs) * alignof(KArgs) + sizeof(KArgs)), ...);
+  return o;
+}
+constexpr size_t kMaxKernarg = 4096;
+static_assert(kernarg_bytes<GemmList, GemmStrideList>() <= kMaxKernarg, "gemm_pop_kernel's arguments");
+static_assert(kernarg_bytes<AdamArgs, int64_t, MemberTable, MemberTable, MemberTable>() <= kMaxKernarg, "adam_pop_hyper_kernel's arguments");
+static_assert(kernarg_bytes<ActorHeadArgs, HeadStride, MemberTable, MemberTable>() <= kMaxKernarg, "actor_head_pop_hyper_kernel's arguments");
+static_assert(kernarg_bytes<CriticHeadArgs, HeadStride, MemberTable>() <= kMaxKernarg, "critic_head_pop_hyper_kernel's arguments");
+static_assert(kernarg_bytes<DaddpgCriticHeadArgs, HeadStride, MemberTable>() <= kMaxKernarg, "daddpg_critic_head_pop_hyper_kernel's arguments");
+static_assert(kernarg_bytes<Datd3ActorHeadArgs, HeadStride, MemberTable, MemberTable>() <= kMaxKernarg,
+              "datd3_actor_head_pop_hyper_kernel's arguments");
+static_assert(kernarg_bytes<Datd3CriticHeadArgs, HeadStride, MemberTable, MemberTable, MemberTable, MemberTable>() <= kMaxKernarg,
+              "datd3_critic_head_pop_hyper_kernel's arguments");
+
+// Args: ArmEnvTd3Args, ArmEnvDaddpgArgs or ArmEnvDatd3Args (beta1, beta2, eps, tau).  `lr` is the args' learning rate of this
+// optimiser and `lr_of` the same field of a member's ArmEnvPopHyper; `loss_w1_of`: the member's field that P.loss_w1 is, or NULL
+// where it is no hyper-parameter.
 template <class Args>
-int launch_adam(AdamArgs &P, float lr, int64_t step, const Args *a, const MemberStrides *pop, hipStream_t s) {
+int launch_adam(AdamArgs &P, float lr, float ArmEnvPopHyper::*lr_of, float ArmEnvPopHyper::*loss_w1_of, int64_t step, const Args *a,
+                const MemberStrides *pop, hipStream_t s) {
   P.beta1 = a->beta1; P.beta2 = a->beta2; P.eps = a->eps; P.tau = a->tau;
   const double bc1 = 1.0 - std::pow((double)a->beta1, (double)step), bc2 = 1.0 - std::pow((double)a->beta2, (double)step);
   P.step_size = (float)(lr / bc1);
   P.bc2_sqrt = (float)std::sqrt(bc2);
   const unsigned blocks = (unsigned)((P.total + 255) / 256) + (P.loss_rows ? 1u : 0u);
-  if (pop)
+  if (pop && pop->hyper) {
+    const float shared_w1 = P.loss_w1;
+    hipLaunchKernelGGL(adam_pop_hyper_kernel, dim3(blocks, (unsigned)pop->members), dim3(256), 0, s, P, pop->ws,
+                       pop->table([=](const ArmEnvPopHyper &h) { return (float)(h.*lr_of / bc1); }), pop->table(&ArmEnvPopHyper::tau),
+                       pop->table([=](const ArmEnvPopHyper &h) { return loss_w1_of ? h.*loss_w1_of : shared_w1; }));
+  } else if (pop)
     hipLaunchKernelGGL(adam_pop_kernel, dim3(blocks, (unsigned)pop->members), dim3(256), 0, s, P, pop->ws);
   else
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, P);
@@ -281,6 +323,26 @@ int check_buffers(const char *fn, const Args *a, std::initializer_list<NamedF> a
   return ARMENV_OK;
 }
 
+// The members' own hyper-parameters of an armenv_*_pop_update_hyper call: of each hyper[p], the fields the agent reads (`noise`: the
+// target-policy noise's two; `darc`: DARC's two) against the ranges of check_buffers, the first one out of range named.
+int check_hyper(const char *fn, const ArmEnvPopHyper *hyper, int members, bool noise, bool darc) {
+  for (int p = 0; p < members; ++p) {
+    const ArmEnvPopHyper &h = hyper[p];
+    const struct { const char *name; float v; bool read, ok; } fields[] = {
+        {"gamma", h.gamma, true, h.gamma >= 0.f && h.gamma <= 1.f},
+        {"tau", h.tau, true, h.tau >= 0.f && h.tau <= 1.f},
+        {"policy_noise", h.policy_noise, noise, h.policy_noise >= 0.f},
+        {"noise_clip", h.noise_clip, noise, h.noise_clip >= 0.f},
+        {"actor_lr", h.actor_lr, true, h.actor_lr >= 0.f},
+        {"critic_lr", h.critic_lr, true, h.critic_lr >= 0.f},
+        {"q_weight", h.q_weight, darc, h.q_weight >= 0.f && h.q_weight <= 1.f},
+        {"regularization_weight", h.regularization_weight, darc, h.regularization_weight >= 0.f}};
+    for (const auto &f : fields)
+      if (f.read && (!std::isfinite(f.v) || !f.ok)) return fail(ARMENV_EINVAL, "%s: hyper[%d].%s = %g out of range", fn, p, f.name, (double)f.v);
+  }
+  return ARMENV_OK;
+}
+
 // the target-policy noise's two, which TD3 and DATD3 / DARC check after tau
 #define LRN_NOISE_HP(a) \
   {"policy_noise", (a)->policy_noise, (a)->policy_noise >= 0.f}, {"noise_clip", (a)->noise_clip, (a)->noise_clip >= 0.f}
@@ -312,8 +374,10 @@ struct Update {
   int critic_soft;             // stage 9: soft-update the stepped critics' targets
   int loss_cols;               // stage 9: columns of the loss rows
   float loss_w1;               //          and the weight of column 1's mean
+  float ArmEnvPopHyper::*loss_w1_of;   //      and, where that weight is a hyper-parameter (DARC), a member's field of it; else NULL
   int64_t loss_rows;           //          and where they are in the workspace
-  const MemberStrides *pop;    // a population update: its member count and strides; NULL: one learner, the single-learner kernels
+  const MemberStrides *pop;    // a population update: its member count, strides and (hyper) the members' own hyper-parameters; NULL:
+                               // one learner, the single-learner kernels
 };
 
 // one launch of a per-row kernel (256 threads: four rows per workgroup)
@@ -324,10 +388,11 @@ int launch_rows(Kernel kernel, unsigned blocks, const KArgs &args, hipStream_t s
   return ARMENV_OK;
 }
 
-// ... and of its population form over (blocks, members)
-template <class Kernel, class KArgs, class KStride>
-int launch_rows_pop(Kernel kernel, unsigned blocks, int members, const KArgs &args, const KStride &strides, hipStream_t s) {
-  hipLaunchKernelGGL(kernel, dim3(blocks, (unsigned)members), dim3(256), 0, s, args, strides);
+// ... and of its population form over (blocks, members); `tables`: the further arguments of a *_pop_hyper_kernel
+template <class Kernel, class KArgs, class KStride, class... Tables>
+int launch_rows_pop(Kernel kernel, unsigned blocks, int members, const KArgs &args, const KStride &strides, hipStream_t s,
+                    const Tables &...tables) {
+  hipLaunchKernelGGL(kernel, dim3(blocks, (unsigned)members), dim3(256), 0, s, args, strides, tables...);
   HIP_TRY(hipGetLastError());
   return ARMENV_OK;
 }
@@ -392,7 +457,7 @@ int run_update(const Args *a, const Update &u, hipStream_t s, ActorHeads actor_h
       adam_tensors(P, *u.Q[i].p, *u.Q[i].m, *u.Q[i].v, *u.Q[i].tp, K1, 1, ws + w.pW1[i], ws + w.pW2[i], ws + w.pW3[i]);
     P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = u.critic_soft;
     P.loss_rows = ws + u.loss_rows; P.loss_cols = u.loss_cols; P.loss_w1 = u.loss_w1; P.B = B; P.inv_b = inv_b; P.loss = a->loss_dev;
-    LRN_TRY(launch_adam(P, a->critic_lr, a->critic_step, a, u.pop, s));
+    LRN_TRY(launch_adam(P, a->critic_lr, &ArmEnvPopHyper::critic_lr, u.loss_w1_of, a->critic_step, a, u.pop, s));
   }
   if (!with_actor) return ARMENV_OK;
 
@@ -429,7 +494,7 @@ int run_update(const Args *a, const Update &u, hipStream_t s, ActorHeads actor_h
   AdamArgs P{};
   adam_tensors(P, act, *u.act.m, *u.act.v, *u.act.tp, D, LRN_A, ws + w.pa1, ws + w.pa2, ws + w.pa3);
   P.splits = (int)w.S; P.split_stride = w.split_stride; P.soft = 1;
-  return launch_adam(P, a->actor_lr, a->actor_step, a, u.pop, s);
+  return launch_adam(P, a->actor_lr, &ArmEnvPopHyper::actor_lr, nullptr, a->actor_step, a, u.pop, s);
 }
 
 }  // namespace
@@ -446,9 +511,11 @@ namespace {
 
 constexpr int kMaxMembers = 64;
 
-// armenv_td3_update (members 1, pop false: the single-learner kernels) and armenv_td3_pop_update (pop true: the population kernels
-// over `members` stacked learners, `a` being member 0's arguments)
-int td3_update(const char *fn, const ArmEnvTd3Args *a, int members, bool pop, const char *ws_fn, void *stream) {
+// armenv_td3_update (members 1, pop false: the single-learner kernels), armenv_td3_pop_update (pop true: the population kernels
+// over `members` stacked learners, `a` being member 0's arguments) and armenv_td3_pop_update_hyper (pop true and `hyper`, the members'
+// own hyper-parameters, set)
+int td3_update(const char *fn, const ArmEnvTd3Args *a, int members, bool pop, const ArmEnvPopHyper *hyper, const char *ws_fn,
+               void *stream) {
   LRN_TRY(check_sizes(fn, a));
   if (a->with_actor != 0 && a->with_actor != 1) return fail(ARMENV_EINVAL, "%s: with_actor must be 0 or 1", fn);
   if (a->critic_step < 1) return fail(ARMENV_EINVAL, "%s: critic_step must be >= 1", fn);
@@ -459,6 +526,7 @@ int td3_update(const char *fn, const ArmEnvTd3Args *a, int members, bool pop, co
       {"q2_m", &a->q2_m}, {"q2_v", &a->q2_v}};
   const int64_t ws_bytes = armenv_td3_workspace_bytes(a->state_dim, a->hidden_dim, a->batch);
   LRN_TRY(check_buffers(fn, a, {LRN_NOISE_HP(a)}, {}, nets, ws_bytes * members, ws_fn));
+  if (hyper) LRN_TRY(check_hyper(fn, hyper, members, true, false));
 
   DeviceGuard guard_(a->device);
   if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
@@ -480,6 +548,7 @@ int td3_update(const char *fn, const ArmEnvTd3Args *a, int members, bool pop, co
   MemberStrides ms;
   if (pop) {
     ms.members = members;
+    ms.hyper = hyper;
     ms.ws = ws_bytes / (int64_t)sizeof(float);
     ms.add(a->workspace_dev, ms.ws);
     for (const ArmEnvMlpRW *m : {&a->actor, &a->target_actor, &a->actor_m, &a->actor_v}) ms.add(*m, D, LRN_A);
@@ -509,9 +578,16 @@ int td3_update(const char *fn, const ArmEnvTd3Args *a, int members, bool pop, co
     return run_update(
         a, u, s,
         [&](unsigned row_blocks) {
-          return launch_rows_pop(actor_head_pop_kernel, row_blocks * (a->with_actor ? 2u : 1u), members, ah, actor_st, s);
+          const unsigned blocks = row_blocks * (a->with_actor ? 2u : 1u);
+          if (hyper)
+            return launch_rows_pop(actor_head_pop_hyper_kernel, blocks, members, ah, actor_st, s, ms.table(&ArmEnvPopHyper::policy_noise),
+                                   ms.table(&ArmEnvPopHyper::noise_clip));
+          return launch_rows_pop(actor_head_pop_kernel, blocks, members, ah, actor_st, s);
         },
-        [&](unsigned row_blocks) { return launch_rows_pop(critic_head_pop_kernel, row_blocks, members, ch, critic_st, s); });
+        [&](unsigned row_blocks) {
+          if (hyper) return launch_rows_pop(critic_head_pop_hyper_kernel, row_blocks, members, ch, critic_st, s, ms.table(&ArmEnvPopHyper::gamma));
+          return launch_rows_pop(critic_head_pop_kernel, row_blocks, members, ch, critic_st, s);
+        });
   }
   return run_update(
       a, u, s, [&](unsigned row_blocks) { return launch_rows(actor_head_kernel, row_blocks * (a->with_actor ? 2u : 1u), ah, s); },
@@ -523,7 +599,7 @@ int td3_update(const char *fn, const ArmEnvTd3Args *a, int members, bool pop, co
 extern "C" {
 
 int armenv_td3_update(const ArmEnvTd3Args *a, void *stream) {
-  return td3_update("armenv_td3_update", a, 1, false, "armenv_td3_workspace_bytes", stream);
+  return td3_update("armenv_td3_update", a, 1, false, nullptr, "armenv_td3_workspace_bytes", stream);
 }
 
 int64_t armenv_td3_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members) {
@@ -536,7 +612,7 @@ int armenv_td3_pop_update(const ArmEnvTd3PopArgs *a, void *stream) {
   static const char *fn = "armenv_td3_pop_update";
   if (!a) return fail(ARMENV_EINVAL, "%s: args is NULL", fn);
   if (a->members < 1 || a->members > kMaxMembers) return fail(ARMENV_EINVAL, "%s: members %d outside 1..%d", fn, (int)a->members, kMaxMembers);
-  return td3_update(fn, &a->one, a->members, true, "armenv_td3_pop_workspace_bytes", stream);
+  return td3_update(fn, &a->one, a->members, true, nullptr, "armenv_td3_pop_workspace_bytes", stream);
 }
 
 int64_t armenv_daddpg_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch) {
@@ -547,8 +623,10 @@ int64_t armenv_daddpg_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int
 
 namespace {
 
-// armenv_daddpg_update (members 1, pop false) and armenv_daddpg_pop_update (pop true, `a` being member 0's arguments), as td3_update
-int daddpg_update(const char *fn, const ArmEnvDaddpgArgs *a, int members, bool pop, const char *ws_fn, void *stream) {
+// armenv_daddpg_update (members 1, pop false), armenv_daddpg_pop_update (pop true, `a` being member 0's arguments) and
+// armenv_daddpg_pop_update_hyper (and `hyper` set), as td3_update
+int daddpg_update(const char *fn, const ArmEnvDaddpgArgs *a, int members, bool pop, const ArmEnvPopHyper *hyper, const char *ws_fn,
+                  void *stream) {
   LRN_TRY(check_sizes(fn, a));
   if (a->update_actor != 1 && a->update_actor != 2) return fail(ARMENV_EINVAL, "%s: update_actor %d must be 1 or 2", fn, a->update_actor);
   if (a->critic_step < 1) return fail(ARMENV_EINVAL, "%s: critic_step must be >= 1", fn);
@@ -560,6 +638,7 @@ int daddpg_update(const char *fn, const ArmEnvDaddpgArgs *a, int members, bool p
       {"critic_v", &a->critic_v}};
   const int64_t ws_bytes = armenv_daddpg_workspace_bytes(a->state_dim, a->hidden_dim, a->batch);
   LRN_TRY(check_buffers(fn, a, {}, {}, nets, ws_bytes * members, ws_fn));
+  if (hyper) LRN_TRY(check_hyper(fn, hyper, members, false, false));
 
   DeviceGuard guard_(a->device);
   if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
@@ -594,6 +673,7 @@ int daddpg_update(const char *fn, const ArmEnvDaddpgArgs *a, int members, bool p
   MemberStrides ms;
   if (pop) {
     ms.members = members;
+    ms.hyper = hyper;
     ms.ws = ws_bytes / (int64_t)sizeof(float);
     ms.add(a->workspace_dev, ms.ws);
     for (const ArmEnvMlpRW *m : {&a->actor1, &a->actor2, &a->target_actor1, &a->target_actor2, &a->actor1_m, &a->actor1_v, &a->actor2_m,
@@ -607,7 +687,11 @@ int daddpg_update(const char *fn, const ArmEnvDaddpgArgs *a, int members, bool p
     return run_update(
         a, u, s,
         [&](unsigned row_blocks) { return launch_rows_pop(daddpg_actor_head_pop_kernel, row_blocks * 3u, members, ah, actor_st, s); },
-        [&](unsigned row_blocks) { return launch_rows_pop(daddpg_critic_head_pop_kernel, row_blocks, members, ch, critic_st, s); });
+        [&](unsigned row_blocks) {
+          if (hyper)
+            return launch_rows_pop(daddpg_critic_head_pop_hyper_kernel, row_blocks, members, ch, critic_st, s, ms.table(&ArmEnvPopHyper::gamma));
+          return launch_rows_pop(daddpg_critic_head_pop_kernel, row_blocks, members, ch, critic_st, s);
+        });
   }
   return run_update(
       a, u, s, [&](unsigned row_blocks) { return launch_rows(daddpg_actor_head_kernel, row_blocks * 3u, ah, s); },
@@ -629,7 +713,7 @@ int64_t pop_bytes(int64_t one, int32_t members) { return members < 1 || members 
 extern "C" {
 
 int armenv_daddpg_update(const ArmEnvDaddpgArgs *a, void *stream) {
-  return daddpg_update("armenv_daddpg_update", a, 1, false, "armenv_daddpg_workspace_bytes", stream);
+  return daddpg_update("armenv_daddpg_update", a, 1, false, nullptr, "armenv_daddpg_workspace_bytes", stream);
 }
 
 int64_t armenv_daddpg_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members) {
@@ -639,7 +723,7 @@ int64_t armenv_daddpg_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim,
 int armenv_daddpg_pop_update(const ArmEnvDaddpgPopArgs *a, void *stream) {
   static const char *fn = "armenv_daddpg_pop_update";
   LRN_TRY(check_members(fn, a));
-  return daddpg_update(fn, &a->one, a->members, true, "armenv_daddpg_pop_workspace_bytes", stream);
+  return daddpg_update(fn, &a->one, a->members, true, nullptr, "armenv_daddpg_pop_workspace_bytes", stream);
 }
 
 int64_t armenv_datd3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch) {
@@ -650,8 +734,10 @@ int64_t armenv_datd3_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int6
 
 namespace {
 
-// armenv_datd3_update (members 1, pop false) and armenv_datd3_pop_update (pop true, `a` being member 0's arguments), as td3_update
-int datd3_update(const char *fn, const ArmEnvDatd3Args *a, int members, bool pop, const char *ws_fn, void *stream) {
+// armenv_datd3_update (members 1, pop false), armenv_datd3_pop_update (pop true, `a` being member 0's arguments) and
+// armenv_datd3_pop_update_hyper (and `hyper` set), as td3_update
+int datd3_update(const char *fn, const ArmEnvDatd3Args *a, int members, bool pop, const ArmEnvPopHyper *hyper, const char *ws_fn,
+                 void *stream) {
   LRN_TRY(check_sizes(fn, a));
   if (a->update_actor != 1 && a->update_actor != 2) return fail(ARMENV_EINVAL, "%s: update_actor %d must be 1 or 2", fn, a->update_actor);
   if (a->darc != 0 && a->darc != 1) return fail(ARMENV_EINVAL, "%s: darc %d must be 0 or 1", fn, a->darc);
@@ -670,6 +756,7 @@ int datd3_update(const char *fn, const ArmEnvDatd3Args *a, int members, bool pop
                         {{"q_weight", darc ? a->q_weight : 0.f, !darc || (a->q_weight >= 0.f && a->q_weight <= 1.f)},
                          {"regularization_weight", darc ? a->regularization_weight : 0.f, !darc || a->regularization_weight >= 0.f}},
                         nets, ws_bytes * members, ws_fn));
+  if (hyper) LRN_TRY(check_hyper(fn, hyper, members, true, darc));
 
   DeviceGuard guard_(a->device);
   if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
@@ -693,6 +780,7 @@ int datd3_update(const char *fn, const ArmEnvDatd3Args *a, int members, bool pop
   u.Qa = u.Q[0].p;
   // target critic k always moves: the actor's loss does not read it
   u.critic_soft = 1; u.loss_cols = darc ? 2 : 1; u.loss_w1 = darc ? a->regularization_weight : 0.f; u.loss_rows = darc ? w.loss2 : w.loss1;
+  if (darc) u.loss_w1_of = &ArmEnvPopHyper::regularization_weight;
 
   Datd3ActorHeadArgs ah{};
   ah.B = B; ah.bound = a->action_bound; ah.policy_noise = a->policy_noise; ah.noise_clip = a->noise_clip;
@@ -715,6 +803,7 @@ int datd3_update(const char *fn, const ArmEnvDatd3Args *a, int members, bool pop
   MemberStrides ms;
   if (pop) {
     ms.members = members;
+    ms.hyper = hyper;
     ms.ws = ws_bytes / (int64_t)sizeof(float);
     ms.add(a->workspace_dev, ms.ws);
     for (const ArmEnvMlpRW *m : {&a->actor1, &a->actor2, &a->target_actor1, &a->target_actor2, &a->actor1_m, &a->actor1_v, &a->actor2_m,
@@ -729,8 +818,21 @@ int datd3_update(const char *fn, const ArmEnvDatd3Args *a, int members, bool pop
     const HeadStride actor_st{ms.ws, (int64_t)LRN_A * LRN_H, LRN_A, B, B * LRN_A}, critic_st{ms.ws, LRN_H, 1, B, 0};
     return run_update(
         a, u, s,
-        [&](unsigned row_blocks) { return launch_rows_pop(datd3_actor_head_pop_kernel, row_blocks * 2u, members, ah, actor_st, s); },
-        [&](unsigned row_blocks) { return launch_rows_pop(datd3_critic_head_pop_kernel, row_blocks, members, ch, critic_st, s); });
+        [&](unsigned row_blocks) {
+          if (hyper)
+            return launch_rows_pop(datd3_actor_head_pop_hyper_kernel, row_blocks * 2u, members, ah, actor_st, s,
+                                   ms.table(&ArmEnvPopHyper::policy_noise), ms.table(&ArmEnvPopHyper::noise_clip));
+          return launch_rows_pop(datd3_actor_head_pop_kernel, row_blocks * 2u, members, ah, actor_st, s);
+        },
+        [&](unsigned row_blocks) {
+          // w_min, w_max and reg as the single path forms them from a->q_weight and a->regularization_weight (read when darc)
+          if (hyper)
+            return launch_rows_pop(datd3_critic_head_pop_hyper_kernel, row_blocks, members, ch, critic_st, s, ms.table(&ArmEnvPopHyper::gamma),
+                                   ms.table(&ArmEnvPopHyper::q_weight),
+                                   ms.table([](const ArmEnvPopHyper &h) { return (float)(1.0 - (double)h.q_weight); }),
+                                   ms.table(&ArmEnvPopHyper::regularization_weight));
+          return launch_rows_pop(datd3_critic_head_pop_kernel, row_blocks, members, ch, critic_st, s);
+        });
   }
   return run_update(
       a, u, s, [&](unsigned row_blocks) { return launch_rows(datd3_actor_head_kernel, row_blocks * 2u, ah, s); },
@@ -742,7 +844,7 @@ int datd3_update(const char *fn, const ArmEnvDatd3Args *a, int members, bool pop
 extern "C" {
 
 int armenv_datd3_update(const ArmEnvDatd3Args *a, void *stream) {
-  return datd3_update("armenv_datd3_update", a, 1, false, "armenv_datd3_workspace_bytes", stream);
+  return datd3_update("armenv_datd3_update", a, 1, false, nullptr, "armenv_datd3_workspace_bytes", stream);
 }
 
 int64_t armenv_datd3_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members) {
@@ -752,7 +854,28 @@ int64_t armenv_datd3_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, 
 int armenv_datd3_pop_update(const ArmEnvDatd3PopArgs *a, void *stream) {
   static const char *fn = "armenv_datd3_pop_update";
   LRN_TRY(check_members(fn, a));
-  return datd3_update(fn, &a->one, a->members, true, "armenv_datd3_pop_workspace_bytes", stream);
+  return datd3_update(fn, &a->one, a->members, true, nullptr, "armenv_datd3_pop_workspace_bytes", stream);
+}
+
+int armenv_td3_pop_update_hyper(const ArmEnvTd3PopArgs *a, const ArmEnvPopHyper *hyper, void *stream) {
+  static const char *fn = "armenv_td3_pop_update_hyper";
+  LRN_TRY(check_members(fn, a));
+  if (!hyper) return fail(ARMENV_EINVAL, "%s: hyper is NULL", fn);
+  return td3_update(fn, &a->one, a->members, true, hyper, "armenv_td3_pop_workspace_bytes", stream);
+}
+
+int armenv_daddpg_pop_update_hyper(const ArmEnvDaddpgPopArgs *a, const ArmEnvPopHyper *hyper, void *stream) {
+  static const char *fn = "armenv_daddpg_pop_update_hyper";
+  LRN_TRY(check_members(fn, a));
+  if (!hyper) return fail(ARMENV_EINVAL, "%s: hyper is NULL", fn);
+  return daddpg_update(fn, &a->one, a->members, true, hyper, "armenv_daddpg_pop_workspace_bytes", stream);
+}
+
+int armenv_datd3_pop_update_hyper(const ArmEnvDatd3PopArgs *a, const ArmEnvPopHyper *hyper, void *stream) {
+  static const char *fn = "armenv_datd3_pop_update_hyper";
+  LRN_TRY(check_members(fn, a));
+  if (!hyper) return fail(ARMENV_EINVAL, "%s: hyper is NULL", fn);
+  return datd3_update(fn, &a->one, a->members, true, hyper, "armenv_datd3_pop_workspace_bytes", stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// armenv_learner_kernels.inc -- the nine kernels of the fused updates (armenv_learner.h), included twice by that header:
+// armenv_learner_kernels.inc -- the nine kernels of the fused updates (armenv_learner.h), included three times by that header:
 //   LRN_POP 0   gemm_kernel, actor_back_kernel, adam_kernel (shared by every update) and the per-row heads actor_head_kernel,
 //               critic_head_kernel (TD3), daddpg_actor_head_kernel, daddpg_critic_head_kernel (DADDPG), datd3_actor_head_kernel,
 //               datd3_critic_head_kernel (DATD3 / DARC): one learner
@@ -6,19 +6,34 @@
 //               (workgroups of one member, members); member p = blockIdx.y works on member 0's problem with every operand moved by
 //               p times its member stride (in elements), and draws its target-policy noise with key seed + p.  The strides are a
 //               second kernel argument.
-// One text, two compilations: the population form is a compile-time variant, the single-learner kernels hold no member arithmetic,
-// and both run the same operations in the same order, which is what makes member p of a population update equal the single update
+//   LRN_POP 2   the *_pop_hyper_kernel forms of the armenv_*_pop_update_hyper entry points: the population form of exactly the
+//               kernels that read a hyper-parameter a member may have of its own -- adam (step_size, tau, loss_w1), the three critic
+//               heads (gamma; DATD3 / DARC: w_min, w_max, reg) and the TD3 and DATD3 actor heads (policy_noise, noise_clip) -- with
+//               every such scalar taken from a per-member table (MemberTable, further by-value kernel arguments) at blockIdx.y.  A
+//               uniform index into the kernel-argument segment: a scalar load, no scratch.  gemm, actor_back and the DADDPG actor
+//               head read none and have no such form.
+// One text, three compilations: the population forms are compile-time variants, the single-learner kernels hold no member arithmetic,
+// and all run the same operations in the same order, which is what makes member p of a population update equal the single update
 // bit for bit.
-#if LRN_POP
+#if LRN_POP == 2
+#define LRN_KERNEL(name) name##_pop_hyper_kernel
+#define LRN_POP_PARAM(decl) , decl
+#define LRN_HYPER_PARAM(...) , __VA_ARGS__
+#define LRN_MEMBER(ptr, stride) ((ptr) + (int64_t)blockIdx.y * (stride))
+#elif LRN_POP
 #define LRN_KERNEL(name) name##_pop_kernel
 #define LRN_POP_PARAM(decl) , decl
+#define LRN_HYPER_PARAM(...)
 #define LRN_MEMBER(ptr, stride) ((ptr) + (int64_t)blockIdx.y * (stride))     // member blockIdx.y's `ptr`
 #else
 #define LRN_KERNEL(name) name##_kernel
 #define LRN_POP_PARAM(decl)
+#define LRN_HYPER_PARAM(...)
 #define LRN_MEMBER(ptr, stride) ptr
 #endif
+#define LRN_OWN(field, table) P.field = table.v[blockIdx.y]     // LRN_POP 2: member blockIdx.y's own value of a scalar of P
 
+#if LRN_POP < 2
 __global__ __launch_bounds__(256) void LRN_KERNEL(gemm)(GemmList L LRN_POP_PARAM(GemmStrideList S)) {
   __shared__ float As[LRN_TK][LRN_TM + 4];
   __shared__ float Bs[LRN_TK][LRN_TN + 4];
@@ -104,9 +119,14 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(gemm)(GemmList L LRN_POP_PARAM
     C[(int64_t)m * G.ldc + n] = v;
   }
 }
+#endif
 
 // blocks [0, ceil(B / 4)): target rows; the next ceil(B / 4): actor rows
-__global__ __launch_bounds__(256) void LRN_KERNEL(actor_head)(ActorHeadArgs P LRN_POP_PARAM(HeadStride S)) {
+__global__ __launch_bounds__(256) void LRN_KERNEL(actor_head)(ActorHeadArgs P LRN_POP_PARAM(HeadStride S)
+                                                              LRN_HYPER_PARAM(MemberTable policy_noise, MemberTable noise_clip)) {
+#if LRN_POP == 2
+  LRN_OWN(policy_noise, policy_noise); LRN_OWN(noise_clip, noise_clip);
+#endif
 #if LRN_POP
   {
     const int64_t p = blockIdx.y;
@@ -135,7 +155,11 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(actor_head)(ActorHeadArgs P LR
 }
 
 // target = r + (1 - d) gamma min(tq1, tq2); loss = mse(q1, target) + mse(q2, target) and its deltas, one wave per row
-__global__ __launch_bounds__(256) void LRN_KERNEL(critic_head)(CriticHeadArgs P LRN_POP_PARAM(HeadStride S)) {
+__global__ __launch_bounds__(256) void LRN_KERNEL(critic_head)(CriticHeadArgs P LRN_POP_PARAM(HeadStride S)
+                                                               LRN_HYPER_PARAM(MemberTable gamma)) {
+#if LRN_POP == 2
+  LRN_OWN(gamma, gamma);
+#endif
 #if LRN_POP
   {
     const int64_t p = blockIdx.y;
@@ -173,6 +197,7 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(critic_head)(CriticHeadArgs P 
 // DADDPG.  blocks [k ceil(B / 4), (k + 1) ceil(B / 4)): rows of problem k; no noise, no clamp (DADDPG_mlp.py:131-134).  The
 // population form moves problem k's pointers where it reads them (LRN_MEMBER): shifting the argument's arrays in place and then
 // indexing them by k would put them in scratch.
+#if LRN_POP < 2
 __global__ __launch_bounds__(256) void LRN_KERNEL(daddpg_actor_head)(DaddpgActorHeadArgs P LRN_POP_PARAM(HeadStride S)) {
   const int lane = threadIdx.x & 63;
   const int64_t nb = (P.B + 3) / 4;
@@ -184,9 +209,14 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(daddpg_actor_head)(DaddpgActor
   if (lane != 0) return;
   store_action(u, P.bound, LRN_MEMBER(P.a[k], S.ws), LRN_MEMBER(P.tanh_out, S.ws), k == 2, b);
 }
+#endif
 
 // DADDPG.  target = r + (1 - d) gamma min(tq(a2_1), tq(a2_2)); loss = mse(q, target) and its deltas, one wave per row
-__global__ __launch_bounds__(256) void LRN_KERNEL(daddpg_critic_head)(DaddpgCriticHeadArgs P LRN_POP_PARAM(HeadStride S)) {
+__global__ __launch_bounds__(256) void LRN_KERNEL(daddpg_critic_head)(DaddpgCriticHeadArgs P LRN_POP_PARAM(HeadStride S)
+                                                                      LRN_HYPER_PARAM(MemberTable gamma)) {
+#if LRN_POP == 2
+  LRN_OWN(gamma, gamma);
+#endif
 #if LRN_POP
   {
     const int64_t p = blockIdx.y;
@@ -216,7 +246,11 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(daddpg_critic_head)(DaddpgCrit
 
 // DATD3 / DARC.  blocks [0, ceil(B / 4)): target rows, one wave computes BOTH proposals of its row from one noise draw; the next
 // ceil(B / 4): actor rows
-__global__ __launch_bounds__(256) void LRN_KERNEL(datd3_actor_head)(Datd3ActorHeadArgs P LRN_POP_PARAM(HeadStride S)) {
+__global__ __launch_bounds__(256) void LRN_KERNEL(datd3_actor_head)(Datd3ActorHeadArgs P LRN_POP_PARAM(HeadStride S)
+                                                                    LRN_HYPER_PARAM(MemberTable policy_noise, MemberTable noise_clip)) {
+#if LRN_POP == 2
+  LRN_OWN(policy_noise, policy_noise); LRN_OWN(noise_clip, noise_clip);
+#endif
 #if LRN_POP
   {
     const int64_t p = blockIdx.y;
@@ -254,7 +288,12 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(datd3_actor_head)(Datd3ActorHe
 
 // DATD3 / DARC.  target = r + (1 - d) gamma T, T = min(tq1, tq2) (darc: w_min T + w_max T); loss = mse(q, target) (darc: + reg
 // mse(q, q_other)) and its deltas, one wave per row
-__global__ __launch_bounds__(256) void LRN_KERNEL(datd3_critic_head)(Datd3CriticHeadArgs P LRN_POP_PARAM(HeadStride S)) {
+__global__ __launch_bounds__(256) void LRN_KERNEL(datd3_critic_head)(Datd3CriticHeadArgs P LRN_POP_PARAM(HeadStride S)
+                                                                     LRN_HYPER_PARAM(MemberTable gamma, MemberTable w_min, MemberTable w_max,
+                                                                                     MemberTable reg)) {
+#if LRN_POP == 2
+  LRN_OWN(gamma, gamma); LRN_OWN(w_min, w_min); LRN_OWN(w_max, w_max); LRN_OWN(reg, reg);     // the last three are read when darc
+#endif
 #if LRN_POP
   {
     const int64_t p = blockIdx.y;
@@ -293,6 +332,7 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(datd3_critic_head)(Datd3Critic
 }
 
 // back through cat(s, a) -> a = bound tanh(u) -> fc3 of the actor, one wave per row
+#if LRN_POP < 2
 __global__ __launch_bounds__(256) void LRN_KERNEL(actor_back)(ActorBackArgs P LRN_POP_PARAM(ActorBackStride S)) {
 #if LRN_POP
   {
@@ -330,8 +370,21 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(actor_back)(ActorBackArgs P LR
   o.w = h.w > 0.f ? du[0] * w0.w + du[1] * w1.w + du[2] * w2.w : 0.f;
   reinterpret_cast<float4 *>(P.da2 + b * LRN_H)[lane] = o;
 }
+#endif
 
-__global__ __launch_bounds__(256) void LRN_KERNEL(adam)(AdamArgs P LRN_POP_PARAM(int64_t ws_stride)) {
+__global__ __launch_bounds__(256) void LRN_KERNEL(adam)(AdamArgs P LRN_POP_PARAM(int64_t ws_stride)
+                                                        LRN_HYPER_PARAM(MemberTable step_size, MemberTable tau, MemberTable loss_w1)) {
+  // P is read where it lies (t[] is indexed by a loop's result: a modified copy of P would live in scratch), so the member's own
+  // scalars are named here and not written into it
+#if LRN_POP == 2
+#define LRN_STEP_SIZE step_size.v[blockIdx.y]
+#define LRN_TAU tau.v[blockIdx.y]
+#define LRN_LOSS_W1 loss_w1.v[blockIdx.y]
+#else
+#define LRN_STEP_SIZE P.step_size
+#define LRN_TAU P.tau
+#define LRN_LOSS_W1 P.loss_w1
+#endif
 #if LRN_POP
   // member p's tensors lie p times their own size (p, m, v, tp: rows x cols; partial and loss_rows: one workspace) behind member 0's,
   // and its loss is loss[p]; the step numbers, and so the bias corrections, are the population's
@@ -366,7 +419,7 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(adam)(AdamArgs P LRN_POP_PARAM
       }
       __syncthreads();
     }
-    if (threadIdx.x == 0 && P.loss) LRN_LOSS[0] = P.loss_cols == 2 ? red[0][0] * P.inv_b + P.loss_w1 * (red[1][0] * P.inv_b) : red[0][0] * P.inv_b;
+    if (threadIdx.x == 0 && P.loss) LRN_LOSS[0] = P.loss_cols == 2 ? red[0][0] * P.inv_b + LRN_LOSS_W1 * (red[1][0] * P.inv_b) : red[0][0] * P.inv_b;
     return;
   }
   if (e >= P.total) return;
@@ -390,13 +443,18 @@ __global__ __launch_bounds__(256) void LRN_KERNEL(adam)(AdamArgs P LRN_POP_PARAM
   const float v = P.beta2 * T.v[i] + (1.0f - P.beta2) * g * g;
   T.m[i] = m;
   T.v[i] = v;
-  const float p = T.p[i] - P.step_size * m / (sqrtf(v) / P.bc2_sqrt + P.eps);
+  const float p = T.p[i] - LRN_STEP_SIZE * m / (sqrtf(v) / P.bc2_sqrt + P.eps);
   T.p[i] = p;
-  if (P.soft) T.tp[i] = T.tp[i] * (1.0f - P.tau) + P.tau * p;
+  if (P.soft) T.tp[i] = T.tp[i] * (1.0f - LRN_TAU) + LRN_TAU * p;
 }
 
 #undef LRN_LOSS_ROWS
 #undef LRN_LOSS
+#undef LRN_STEP_SIZE
+#undef LRN_TAU
+#undef LRN_LOSS_W1
 #undef LRN_KERNEL
 #undef LRN_MEMBER
 #undef LRN_POP_PARAM
+#undef LRN_HYPER_PARAM
+#undef LRN_OWN

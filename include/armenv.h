@@ -44,6 +44,8 @@ extern "C" {
                                      ArmEnvDaddpgPopArgs / ArmEnvDatd3PopArgs, additive in the same way;
                                      still 8: + armenv_her_pop_sample, armenv_pop_count_episodes, armenv_pop_write_episodes and
                                      ArmEnvHerPopArgs, additive in the same way;
+                                     still 8: + armenv_td3_pop_update_hyper, armenv_daddpg_pop_update_hyper,
+                                     armenv_datd3_pop_update_hyper and ArmEnvPopHyper, additive in the same way;
                                   7: + armenv_td3_update, armenv_td3_workspace_bytes, ArmEnvMlpRW, ArmEnvTd3Args;
                                   6: + armenv_set_policy_daddpg, armenv_episode_returns_f32, ARMENV_POLICY_DADDPG; ArmEnvConfig unchanged since 5 */
 
@@ -520,7 +522,8 @@ int armenv_td3_update(const ArmEnvTd3Args *args, void *stream);
 
 /* ---- a population of TD3 learners: ONE armenv_td3_update for each of P independent learners ("members") in one launch sequence --
  * as many launches as for one learner (9, 16 with the actor step), each over P times the workgroups.  Members share the
- * hyper-parameters, the step numbers (so Adam's bias corrections) and with_actor, and nothing else.
+ * hyper-parameters, the step numbers (so Adam's bias corrections) and with_actor, and nothing else; armenv_td3_pop_update_hyper
+ * (below) gives every member its own gamma, tau, noise pair and learning rates.
  *
  * Stacked tensors: every array that `one` names is member 0's array of a contiguous stack with a leading member dimension, and
  * member p's array lies p times the array's own size behind it.  There are no stride arguments:
@@ -632,7 +635,8 @@ int armenv_datd3_update(const ArmEnvDatd3Args *args, void *stream);
  *   states_dev, next_states_dev [P][B][state_dim];  actions_dev [P][B][3];  rewards_dev, dones_dev [P][B]
  *   noise_dev (DATD3 / DARC, nullable) [P][B][3];  loss_dev (nullable) [P]
  *   workspace_dev: P consecutive single-learner workspaces
- * Members share the hyper-parameters, update_actor, darc, q_weight, regularization_weight and both step numbers, and nothing else.
+ * Members share the hyper-parameters, update_actor, darc, q_weight, regularization_weight and both step numbers, and nothing else;
+ * the *_pop_update_hyper entry points (below) give every member its own gamma, tau, noise pair, learning rates and DARC weights.
  * DATD3 / DARC: member p draws its noise with Philox key seed + p (mod 2^64) and the unchanged counter (row, draw), once per row for
  * both proposals.  Every sum keeps the single update's order, so member p's results equal, bit for bit, the single entry point on
  * member p's arrays (DATD3 / DARC: with seed + p).
@@ -655,6 +659,33 @@ typedef struct ArmEnvDatd3PopArgs {
 /* members x armenv_datd3_workspace_bytes(state_dim, hidden_dim, batch); -1 for unsupported sizes or members outside 1..64. */
 int64_t armenv_datd3_pop_workspace_bytes(int32_t state_dim, int32_t hidden_dim, int64_t batch, int32_t members);
 int armenv_datd3_pop_update(const ArmEnvDatd3PopArgs *args, void *stream);
+
+/* ---- per-member hyper-parameters: the three population updates above with member p reading ITS OWN gamma, tau, policy_noise,
+ * noise_clip, actor_lr, critic_lr, q_weight and regularization_weight -- a sweep of learning rates, discounts, Polyak rates or DARC's
+ * two weights at the price of one update.  `args` is the matching *_pop_update's, unchanged; `hyper` is a HOST array of
+ * args->members entries, read during the call: hyper[p]'s values replace the same-named fields of `one` for member p (the fields of
+ * `one` are still checked, and are what a member would read if its entry equalled them).  The values travel to the kernels as
+ * by-value kernel arguments beside the member strides -- no device allocation, copy, memset or host synchronisation, so the call
+ * stays capturable; a captured graph keeps the values of capture time.
+ * Members still share action_bound, Adam's beta1, beta2 and eps, both step numbers (so the bias corrections), with_actor,
+ * update_actor, darc, seed and draw, and the shapes.
+ * Member p's results equal, bit for bit, the SINGLE entry point (armenv_td3_update, ...) on member p's arrays with hyper[p]'s values
+ * written into its struct and, where the agent draws noise, seed + p: each member's derived scalars (Adam's step size lr / (1 -
+ * beta1^step), DARC's 1 - q_weight, the loss's weight) are formed by the single path's own expressions.  When every hyper[p] equals
+ * `one`'s fields the result is *_pop_update's, bit for bit.  The launch count is one update's: 9 or 16.  The workspace is the
+ * *_pop_workspace_bytes of the matching update.
+ * Refused before any HIP call (ARMENV_EINVAL): whatever the matching *_pop_update refuses, `hyper` NULL, and for each member the
+ * fields its agent reads outside the single entry point's ranges -- gamma, tau, q_weight in [0, 1]; the learning rates, policy_noise,
+ * noise_clip, regularization_weight >= 0 and finite; NaN is refused -- named as hyper[p].field in armenv_last_error().  Fields an
+ * agent does not read are ignored, as the single entry points ignore them: DADDPG ignores policy_noise, noise_clip, q_weight and
+ * regularization_weight; DATD3 without `darc` ignores the last two. */
+typedef struct ArmEnvPopHyper {   /* ONE member's values */
+  float gamma, tau, policy_noise, noise_clip, actor_lr, critic_lr, q_weight, regularization_weight;
+} ArmEnvPopHyper;
+
+int armenv_td3_pop_update_hyper(const ArmEnvTd3PopArgs *args, const ArmEnvPopHyper *hyper, void *stream);
+int armenv_daddpg_pop_update_hyper(const ArmEnvDaddpgPopArgs *args, const ArmEnvPopHyper *hyper, void *stream);
+int armenv_datd3_pop_update_hyper(const ArmEnvDatd3PopArgs *args, const ArmEnvPopHyper *hyper, void *stream);
 
 /* Measurement aid (bench.py's roofline.valu.one_wave_per_simd; no reference counterpart): the interval at which SIMDs issue
  * independent 64-lane v_fma_f64 (precision 64) / v_fma_f32 (32) instructions when every SIMD of `device` holds
