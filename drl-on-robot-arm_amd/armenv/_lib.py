@@ -133,6 +133,14 @@ class ArmEnvPopHyper(C.Structure):
                                          "regularization_weight")]
 
 
+EXPLOIT_MAX_TENSORS = 128
+
+
+class ArmEnvPopExploitArgs(C.Structure):
+    _fields_ = [("device", C.c_int32), ("members", C.c_int32), ("tensors", C.c_int32), ("reserved", C.c_int32),
+                ("src", C.POINTER(C.c_int32)), ("base", C.POINTER(C.c_void_p)), ("elems", C.POINTER(C.c_int64))]
+
+
 # every symbol include/armenv.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -181,6 +189,7 @@ SYMBOLS = {
     "armenv_td3_pop_update_hyper": (C.c_int, [C.POINTER(ArmEnvTd3PopArgs), C.POINTER(ArmEnvPopHyper), _P]),
     "armenv_daddpg_pop_update_hyper": (C.c_int, [C.POINTER(ArmEnvDaddpgPopArgs), C.POINTER(ArmEnvPopHyper), _P]),
     "armenv_datd3_pop_update_hyper": (C.c_int, [C.POINTER(ArmEnvDatd3PopArgs), C.POINTER(ArmEnvPopHyper), _P]),
+    "armenv_pop_exploit": (C.c_int, [C.POINTER(ArmEnvPopExploitArgs), _P]),
     "armenv_probe_issue_rate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "armenv_probe_clock": (C.c_int, [C.c_int32, _P, C.POINTER(C.c_int32), _P]),
     "armenv_num_envs": (C.c_int64, [_P]),

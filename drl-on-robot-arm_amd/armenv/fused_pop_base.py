@@ -6,7 +6,8 @@ export_member.  The step schedule is the agent's own, shared with its single lea
 
 Per-member hyper-parameters: every constructor takes, for each of its agent's ``sweepable()`` names (the learning rates, tau, gamma,
 the target-policy noise's two, DARC's two weights), a scalar for all members or a sequence of P values; ``hyper(p)`` / ``set_hyper(p,
-...)`` read and change one member's, ``copy_member`` is the exploit step of a population-based schedule.  While every member holds
+...)`` read and change one member's, ``copy_member`` is the exploit step of a population-based schedule for one member and
+``exploit(src)`` the same for a whole plan in ONE launch (armenv_pop_exploit); armenv.pbt makes the plans.  While every member holds
 the same values the update is armenv_<algo>_pop_update, as before; once two members differ it is armenv_<algo>_pop_update_hyper,
 which hands each member's values to the kernels.  Members always share the step schedule (so ``policy_freq``), Adam's constants,
 ``action_bound`` and the shapes."""
@@ -37,6 +38,25 @@ def _values(value):
         return [float(v) for v in value]
     except TypeError:                                   # a 0-dim array or tensor
         return None
+
+
+def check_plan(who, src, members):
+    """An exploit plan as a list of `members` ints: member p becomes a copy of member src[p].  armenv_pop_exploit's rules, checked
+    on the host: one entry per member, each a member's index, and no source that is itself replaced (src[src[p]] == src[p]), so the
+    outcome does not depend on the order of the copies.  ValueError otherwise."""
+    try:
+        plan = [int(v) for v in src]
+    except (TypeError, ValueError):
+        raise ValueError("%s: src must be a sequence of %d member indices" % (who, members)) from None
+    if len(plan) != members or any(v != w for v, w in zip(plan, src)):
+        raise ValueError("%s: src must be a sequence of %d member indices" % (who, members))
+    for p, v in enumerate(plan):
+        if not 0 <= v < members:
+            raise ValueError("%s: src[%d] = %d outside 0..%d" % (who, p, v, members - 1))
+    for p, v in enumerate(plan):
+        if plan[v] != v:
+            raise ValueError("%s: src[%d] = %d is itself replaced (src[%d] = %d)" % (who, p, v, v, plan[v]))
+    return plan
 
 
 class TwoActorMember:
@@ -154,6 +174,35 @@ class FusedPopulation(FusedLearner):
         if hyper:
             self._rows[dst] = dict(self._rows[src])
             self._hyper_changed()
+
+    def exploit(self, src, hyper=True):
+        """The exploit step of population-based training for all members at once: member p becomes a copy of member ``src[p]`` --
+        nets, targets and Adam moments, every tensor of ``stacks`` -- in ONE launch (armenv_pop_exploit) on the current stream, and,
+        with `hyper`, takes its source's hyper-parameters.  ``src[p] == p`` keeps member p.  The plan is checked first and a bad one
+        (a wrong length, an index that is no member's, a source that is itself replaced) raises ValueError with nothing moved.  The
+        step counters are the population's and stay; a member keeps its own noise seed, ``seed + p``.  Follow with
+        ``set_hyper(p, ...)`` on the replaced members to explore.  Returns the list of the replaced members."""
+        who = type(self).__name__ + ".exploit"
+        plan = check_plan(who, src, self.members)
+        replaced = [p for p, v in enumerate(plan) if v != p]
+        if not replaced:
+            return replaced
+        if self.device.type != "cuda":
+            raise RuntimeError("%s: the stacks are on %s; armenv_pop_exploit copies on a HIP device" % (who, self.device))
+        tensors = [t for six in self.stacks.values() for t in six]
+        a = L.ArmEnvPopExploitArgs()
+        a.device = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        a.members, a.tensors = self.members, len(tensors)
+        src_c = (C.c_int32 * self.members)(*plan)
+        base_c = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+        elems_c = (C.c_int64 * len(tensors))(*[t[0].numel() for t in tensors])
+        a.src, a.base, a.elems = src_c, base_c, elems_c
+        L.check(L.load().armenv_pop_exploit(C.byref(a), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        if hyper:
+            for p in replaced:
+                self._rows[p] = dict(self._rows[plan[p]])
+            self._hyper_changed()
+        return replaced
 
     def _bind(self, args):
         super()._bind(args)

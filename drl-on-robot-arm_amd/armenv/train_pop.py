@@ -8,10 +8,17 @@ update is one ``train`` = two reference updates on the batch, as in armenv.train
     python -m armenv.train_pop --members 16 --iterations 200
     python -m armenv.train_pop --members 16 --iterations 200 --algo daddpg
     python -m armenv.train_pop --members 4 --sweep actor_lr=1e-3,5e-4,2e-4,1e-4 --sweep tau=0.005,0.005,0.01,0.01
+    python -m armenv.train_pop --members 8 --iterations 60 --pbt-every 10
 
 ``sweep`` (``--sweep NAME=v0,v1,...``, one value per member): the members' own values of the agent's sweepable hyper-parameters
 (``sweepable_names(algo)``: the learning rates, tau, gamma, the target-policy noise's two, DARC's two weights) and of ``expl_sigma``,
 the rollout's exploration sigma -- a hyper-parameter sweep at the price of one run; every history record then carries them.
+
+``pbt`` (``--pbt-every N``, ``--pbt-fraction F``, ``--pbt-perturb LO,HI``): population-based training, armenv.pbt.PBTSchedule.  After
+every N iterations the members are ranked by their success rate since the last such step; the bottom fraction become copies of
+members of the top (``pop.exploit``: nets, targets, moments and hyper-parameters, ONE launch) and their hyper-parameters -- and
+``expl_sigma`` -- are perturbed (``explore``).  A replaced member keeps its environments, its replay ring and its noise seed.  Each
+step is logged and kept in the history as a ``kind="pbt"`` record; every record then carries the members' current values.
 
 Member p has its own environments, trajectory store, initial weights and noise, all seeded ``seed + p``.  Rollouts are P launches,
 one per member, each with that member's policy (TD3: its actor; the two-actor agents: their own take_action, fused into the rollout
@@ -31,6 +38,7 @@ import time
 from .fused_daddpg_pop import FusedDADDPGPopulation
 from .fused_datd3_pop import FusedDARCPopulation, FusedDATD3Population
 from .fused_td3_pop import FusedTD3Population
+from .pbt import PBTSchedule
 from .replay import PopulationTrajectoryStore, TrajectoryStore
 from .train import _TASKS, ALGOS, _install_policy
 
@@ -56,16 +64,34 @@ def _checked_sweep(sweep, algo, members):
     return out
 
 
+def _checked_pbt(pbt, algo, members, seed=0):
+    """`pbt` (None, a PBTSchedule or a dict of its arguments, whose ``seed`` defaults to `seed`) as a schedule bound to agent
+    `algo`'s names, or None; ValueError for arguments that PBTSchedule refuses, a name the agent does not have, or a population of
+    one"""
+    if pbt is None:
+        return None
+    if not isinstance(pbt, PBTSchedule):
+        pbt = PBTSchedule(**dict(dict(seed=seed), **pbt))
+    if members < 2:
+        raise ValueError("pbt: population-based training needs members >= 2, not %d" % members)
+    return pbt.bind(sweepable_names(algo))
+
+
 def train_reach_population(members=16, num_envs=64, iterations=200, rollout_steps=32, updates=40, batch_size=256, her_ratio=0.8,
                            seed=0, device="cuda:0", actor_kind="actor_f16x3", expl_sigma=None, log_every=10, log=print,
                            window_steps=1536, minimal_episodes=5, max_steps=500, task="reach", algo="td3", store="population",
-                           sweep=None):
+                           sweep=None, pbt=None):
     """Returns (population, history); a history record holds the members' success rates over the last ``log_every`` iterations.
     ``task="push" | "pick"``: armenv.train.train_push's settings (state_dim 9, action_bound 0.4, unclipped exploration noise).
     ``algo``: the agent; the two-actor agents explore as armenv.train has them explore on that task (the same sigma and clip).
     ``store``: "population" (one PopulationTrajectoryStore) or "members" (P TrajectoryStores); both train the same bits.
     ``sweep``: a dict from a name of ``sweepable_names(algo)`` to one value per member; every record then holds it as ``hyper``.
-    Without it the members share every hyper-parameter and the records and the trained bits are what they always were."""
+    Without it the members share every hyper-parameter and the records and the trained bits are what they always were.
+    ``pbt``: an armenv.pbt.PBTSchedule, or a dict of its arguments (``dict(every=10)``; its seed defaults to `seed`):
+    population-based training over the members, which must be two at least; checked, like ``sweep``, before anything is created on
+    the device.  The history then also holds one ``kind="pbt"`` record per PBT step -- iteration, the fitness (success rates since
+    the last step), ``src`` and the replaced members' new values -- and every record holds the members' current values as
+    ``hyper``.  Without it the loop, the records and the trained bits are what they are without the argument."""
     if task not in _TASKS:
         raise ValueError("task must be one of %s" % ", ".join(_TASKS))
     if algo not in ALGOS:
@@ -77,7 +103,8 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
     noise_clip = action_bound if task == "reach" else 1e9
     P = int(members)
     sweep = _checked_sweep(sweep, algo, P)
-    sigmas = sweep.get("expl_sigma", [sigma] * P)
+    pbt = _checked_pbt(pbt, algo, P, seed)
+    sigmas = list(sweep.get("expl_sigma", [sigma] * P))
     pop = _POPULATIONS[algo](P, state_dim, 3, action_bound, device=device, seed=seed,
                              **{name: values for name, values in sweep.items() if name != "expl_sigma"})
     es = [Env(num_envs, device=device, seed=seed + p, max_steps=max_steps) for p in range(P)]
@@ -92,7 +119,18 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
         slices = [pop.member_buffers(p) for p in range(P)]
         bufs = [{} for _ in range(P)]
     prev = [e.counters() for e in es]
+    prev_pbt = prev
     history = []
+
+    def rows():
+        """the members' current values: the population's own and the rollout's sigma"""
+        return [dict(pop.hyper(p), expl_sigma=sigmas[p]) for p in range(P)]
+
+    def current():
+        """... as a history record holds them: by name, for the swept and the perturbed names"""
+        names = [n for n in sweepable_names(algo) if n in sweep or n in pbt.names]
+        return {n: [row[n] for row in rows()] for n in names}
+
     t0 = time.perf_counter()
     for it in range(iterations):
         if store == "population":
@@ -126,8 +164,25 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
             prev = cs
             rec = dict(iteration=it + 1, env_steps=sum(c["env_steps"] for c in cs), episodes=[c["episodes"] for c in cs],
                        success_rate=rates, wall_s=time.perf_counter() - t0)
-            if sweep:
+            if pbt:
+                rec["hyper"] = current()
+            elif sweep:
                 rec["hyper"] = sweep
+            history.append(rec)
+            log(json.dumps(rec))
+        if pbt and pbt.due(it + 1):
+            cs = [e.counters() for e in es]
+            fitness = [(c["successes"] - c0["successes"]) / max(1, c["episodes"] - c0["episodes"]) for c, c0 in zip(cs, prev_pbt)]
+            prev_pbt = cs
+            src, new = pbt.step(fitness, rows())
+            if new:
+                pop.exploit(src, hyper=True)
+                for p, row in new.items():
+                    sigmas[p] = row.pop("expl_sigma")
+                    pop.set_hyper(p, **row)
+            rec = dict(kind="pbt", iteration=it + 1, fitness=fitness, src=src,
+                       new=[dict(member=p, source=src[p], hyper=dict(pop.hyper(p), expl_sigma=sigmas[p])) for p in new],
+                       hyper=current())
             history.append(rec)
             log(json.dumps(rec))
     for e in es:
@@ -153,7 +208,19 @@ def main():
                     help="population: one stacked store, indexed and sampled in one launch each; members: one store per member")
     ap.add_argument("--sweep", action="append", default=[], metavar="NAME=v0,v1,...",
                     help="the members' own values of a hyper-parameter (or of expl_sigma), exactly --members of them; repeatable")
+    ap.add_argument("--pbt-every", type=int, default=None, metavar="N",
+                    help="population-based training: after every N iterations the bottom members copy top members and perturb "
+                         "their hyper-parameters")
+    ap.add_argument("--pbt-fraction", type=float, default=0.25, metavar="F", help="the bottom's (and the top's) share of the members, in (0, 0.5]")
+    ap.add_argument("--pbt-perturb", default="0.8,1.2", metavar="LO,HI", help="the two factors a perturbed value is multiplied by")
     a = ap.parse_args()
+    pbt = None
+    if a.pbt_every is not None:
+        try:
+            pbt = _checked_pbt(dict(every=a.pbt_every, fraction=a.pbt_fraction, perturb=[float(v) for v in a.pbt_perturb.split(",")]),
+                                a.algo, a.members, a.seed)
+        except ValueError as e:
+            ap.error("--pbt-*: %s" % e)
     sweep = {}
     for item in a.sweep:
         name, _, values = item.partition("=")
@@ -167,7 +234,7 @@ def main():
         ap.error(str(e))
     train_reach_population(a.members, a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed,
                            actor_kind=a.actor, window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, algo=a.algo, store=a.store,
-                           sweep=sweep or None)
+                           sweep=sweep or None, pbt=pbt)
 
 
 if __name__ == "__main__":

@@ -29,6 +29,8 @@
 // the member of a population of stacked learners, and as the *_pop_hyper_kernel forms of the armenv_*_pop_update_hyper entry points,
 // where adam and the heads that read a hyper-parameter take it from a per-member table.  This header holds their argument structs and
 // the per-row pieces they are built from.
+// A tenth kernel, pop_exploit_kernel (armenv_pop_exploit), is written once at the end of this header: it copies whole members of
+// the populations' stacks, source to destination, in one launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -322,6 +324,67 @@ struct MemberTable {
 #define LRN_POP 2
 #include "armenv_learner_kernels.inc"
 #undef LRN_POP
+
+// pop_exploit_kernel (armenv_pop_exploit): the exploit step of population-based training.  Member blockIdx.y of every stack
+// [P][elems] of the table becomes a copy of member src.v[blockIdx.y]; a member that is its own source returns at once.  Grid
+// (blocks over one member's elements of all tensors, members): tensor t owns the blocks from t.first on, one block per
+// LRN_EXPLOIT_CHUNK floats.  The host refuses a plan in which a source is itself replaced, so no block reads what another writes.
+constexpr int LRN_EXPLOIT_MAX_TENSORS = 128;
+constexpr int LRN_EXPLOIT_CHUNK = 4096;    // floats per block: four float4 per thread (pop_exploit_kernel spells the four out)
+
+struct ExploitTensor {
+  float *base;       // member 0's array of the stack
+  int64_t elems;     // floats per member = the member stride
+  int32_t first;     // the tensor's first block
+};
+
+struct ExploitTable {
+  ExploitTensor t[LRN_EXPLOIT_MAX_TENSORS];
+  int32_t n;
+};
+
+struct ExploitSources {
+  int32_t v[LRN_MAX_MEMBERS];
+};
+
+__global__ __launch_bounds__(256) void pop_exploit_kernel(ExploitTable T, ExploitSources src) {
+  const int dst = (int)blockIdx.y, from_member = src.v[blockIdx.y];
+  if (from_member == dst) return;
+  // the last tensor whose first block is not after this one (wave-uniform: the table is read where it lies)
+  int lo = 0, hi = T.n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (T.t[mid].first <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const int64_t elems = T.t[lo].elems;
+  const int64_t start = (int64_t)((int)blockIdx.x - T.t[lo].first) * LRN_EXPLOIT_CHUNK;
+  if (start >= elems) return;
+  const int n = (int)(elems - start < LRN_EXPLOIT_CHUNK ? elems - start : LRN_EXPLOIT_CHUNK);
+  const float *from = T.t[lo].base + (int64_t)from_member * elems + start;
+  float *to = T.t[lo].base + (int64_t)dst * elems + start;
+  // A member's base is only 4-byte aligned where elems is no multiple of 4 (a b3 of 1 or 3 floats): float4 where both sides allow
+  // it, with the chunk's last n % 4 floats one by one; else float by float.
+  if ((((uintptr_t)from | (uintptr_t)to) & 15) == 0) {
+    const int n4 = n >> 2;
+    // all of the thread's loads are in flight before its first store
+    const float4 *from4 = reinterpret_cast<const float4 *>(from);
+    float4 *to4 = reinterpret_cast<float4 *>(to);
+    const int i0 = (int)threadIdx.x, i1 = i0 + 256, i2 = i0 + 512, i3 = i0 + 768;
+    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0, r3 = r0;
+    if (i0 < n4) r0 = from4[i0];
+    if (i1 < n4) r1 = from4[i1];
+    if (i2 < n4) r2 = from4[i2];
+    if (i3 < n4) r3 = from4[i3];
+    if (i0 < n4) to4[i0] = r0;
+    if (i1 < n4) to4[i1] = r1;
+    if (i2 < n4) to4[i2] = r2;
+    if (i3 < n4) to4[i3] = r3;
+    const int i = 4 * n4 + (int)threadIdx.x;
+    if (i < n) to[i] = from[i];
+  } else {
+    for (int i = (int)threadIdx.x; i < n; i += 256) to[i] = from[i];
+  }
+}
 
 }  // namespace learner
 }  // namespace armenv

@@ -44,6 +44,10 @@
 // a HOST array ArmEnvPopHyper[P] of the members' own hyper-parameters (MemberStrides.hyper).  Stages 3, 6, 9 and 16 -- the only ones
 // whose kernels read such a scalar -- launch their *_pop_hyper_kernel forms with the members' values as MemberTable arguments, each
 // derived scalar formed per member by the single path's expression; every other launch is the population's.
+//
+// armenv_pop_exploit: the exploit step of population-based training over any population's stacks -- ONE launch of pop_exploit_kernel
+// (armenv_learner.h) in which member p of every stack becomes a copy of member src[p].  The whole plan is checked first; a source
+// that is itself replaced is refused, so the launch has no read that races a write.
 #include <cmath>
 #include <initializer_list>
 
@@ -246,6 +250,8 @@ static_assert(kernarg_bytes<Datd3ActorHeadArgs, HeadStride, MemberTable, MemberT
               "datd3_actor_head_pop_hyper_kernel's arguments");
 static_assert(kernarg_bytes<Datd3CriticHeadArgs, HeadStride, MemberTable, MemberTable, MemberTable, MemberTable>() <= kMaxKernarg,
               "datd3_critic_head_pop_hyper_kernel's arguments");
+static_assert(kernarg_bytes<ExploitTable, ExploitSources>() <= kMaxKernarg, "pop_exploit_kernel's arguments");
+static_assert(LRN_EXPLOIT_MAX_TENSORS == ARMENV_EXPLOIT_MAX_TENSORS, "the header's bound is the table's");
 
 // Args: ArmEnvTd3Args, ArmEnvDaddpgArgs or ArmEnvDatd3Args (beta1, beta2, eps, tau).  `lr` is the args' learning rate of this
 // optimiser and `lr_of` the same field of a member's ArmEnvPopHyper; `loss_w1_of`: the member's field that P.loss_w1 is, or NULL
@@ -876,6 +882,48 @@ int armenv_datd3_pop_update_hyper(const ArmEnvDatd3PopArgs *a, const ArmEnvPopHy
   LRN_TRY(check_members(fn, a));
   if (!hyper) return fail(ARMENV_EINVAL, "%s: hyper is NULL", fn);
   return datd3_update(fn, &a->one, a->members, true, hyper, "armenv_datd3_pop_workspace_bytes", stream);
+}
+
+int armenv_pop_exploit(const ArmEnvPopExploitArgs *a, void *stream) {
+  static const char *fn = "armenv_pop_exploit";
+  if (!a) return fail(ARMENV_EINVAL, "%s: args is NULL", fn);
+  if (!a->src) return fail(ARMENV_EINVAL, "%s: src is NULL", fn);
+  if (!a->base) return fail(ARMENV_EINVAL, "%s: base is NULL", fn);
+  if (!a->elems) return fail(ARMENV_EINVAL, "%s: elems is NULL", fn);
+  if (a->device < 0) return fail(ARMENV_EINVAL, "%s: device %d", fn, (int)a->device);
+  if (a->members < 1 || a->members > kMaxMembers) return fail(ARMENV_EINVAL, "%s: members %d outside 1..%d", fn, (int)a->members, kMaxMembers);
+  if (a->tensors < 1 || a->tensors > LRN_EXPLOIT_MAX_TENSORS)
+    return fail(ARMENV_EINVAL, "%s: tensors %d outside 1..%d", fn, (int)a->tensors, LRN_EXPLOIT_MAX_TENSORS);
+  ExploitTable T{};
+  int64_t blocks = 0;
+  for (int t = 0; t < a->tensors; ++t) {
+    if (!a->base[t]) return fail(ARMENV_EINVAL, "%s: base[%d] is NULL", fn, t);
+    if (a->elems[t] < 1) return fail(ARMENV_EINVAL, "%s: elems[%d] = %lld must be >= 1", fn, t, (long long)a->elems[t]);
+    T.t[t] = ExploitTensor{a->base[t], a->elems[t], (int32_t)blocks};
+    blocks += (a->elems[t] - 1) / LRN_EXPLOIT_CHUNK + 1;
+    if (blocks > INT32_MAX) return fail(ARMENV_EINVAL, "%s: elems[0..%d] need more than %d blocks", fn, t, INT32_MAX);
+  }
+  T.n = a->tensors;
+  ExploitSources S{};
+  bool identity = true;
+  for (int p = 0; p < a->members; ++p) {
+    const int32_t s = a->src[p];
+    if (s < 0 || s >= a->members) return fail(ARMENV_EINVAL, "%s: src[%d] = %d outside 0..%d", fn, p, (int)s, (int)a->members - 1);
+    S.v[p] = s;
+    identity = identity && s == p;
+  }
+  // a source must keep itself: no block of the launch then reads what another block writes
+  for (int p = 0; p < a->members; ++p)
+    if (a->src[a->src[p]] != a->src[p])
+      return fail(ARMENV_EINVAL, "%s: src[%d] = %d is itself replaced (src[%d] = %d)", fn, p, (int)a->src[p], (int)a->src[p],
+                  (int)a->src[a->src[p]]);
+  if (identity) return ARMENV_OK;
+
+  DeviceGuard guard_(a->device);
+  if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", fn, (int)a->device);
+  hipLaunchKernelGGL(pop_exploit_kernel, dim3((unsigned)blocks, (unsigned)a->members), dim3(256), 0, static_cast<hipStream_t>(stream), T, S);
+  HIP_TRY(hipGetLastError());
+  return ARMENV_OK;
 }
 
 }  // extern "C"

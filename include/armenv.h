@@ -46,6 +46,7 @@ extern "C" {
                                      ArmEnvHerPopArgs, additive in the same way;
                                      still 8: + armenv_td3_pop_update_hyper, armenv_daddpg_pop_update_hyper,
                                      armenv_datd3_pop_update_hyper and ArmEnvPopHyper, additive in the same way;
+                                     still 8: + armenv_pop_exploit and ArmEnvPopExploitArgs, additive in the same way;
                                   7: + armenv_td3_update, armenv_td3_workspace_bytes, ArmEnvMlpRW, ArmEnvTd3Args;
                                   6: + armenv_set_policy_daddpg, armenv_episode_returns_f32, ARMENV_POLICY_DADDPG; ArmEnvConfig unchanged since 5 */
 
@@ -686,6 +687,26 @@ typedef struct ArmEnvPopHyper {   /* ONE member's values */
 int armenv_td3_pop_update_hyper(const ArmEnvTd3PopArgs *args, const ArmEnvPopHyper *hyper, void *stream);
 int armenv_daddpg_pop_update_hyper(const ArmEnvDaddpgPopArgs *args, const ArmEnvPopHyper *hyper, void *stream);
 int armenv_datd3_pop_update_hyper(const ArmEnvDatd3PopArgs *args, const ArmEnvPopHyper *hyper, void *stream);
+
+/* ---- the exploit step of population-based training: member p of every stack becomes a copy of member src[p], for all members and
+ * all stacks in ONE kernel launch over (elements, members) -- no memcpy, memset, allocation or host synchronisation, so the call is
+ * capturable.  A stack is any contiguous float array [members][elems]: the nets, targets and Adam moments that the *_pop_update
+ * entry points read, in any number up to ARMENV_EXPLOIT_MAX_TENSORS.  src, base and elems are HOST arrays, read during the call;
+ * base[t] is a device pointer.  A member's base need only be 4-byte aligned and elems need not be a multiple of 4: the copy is
+ * 16 bytes wide where both sides are 16-byte aligned and float by float elsewhere.  The copies are bitwise.
+ * The whole plan is checked before any HIP call (ARMENV_EINVAL, the field named in armenv_last_error()): NULL args, src, base or
+ * elems; device < 0; members outside 1..64; tensors outside 1..ARMENV_EXPLOIT_MAX_TENSORS; a NULL base[t]; elems[t] < 1 (or so large
+ * that the launch would need more than 2^31 - 1 blocks); src[p] outside 0..members-1; and src[src[p]] != src[p], a source that is
+ * itself replaced -- so no read of the launch can race a write and the result does not depend on any order.  An identity plan
+ * (src[p] == p for all p) returns ARMENV_OK without launching, and without touching the device. */
+#define ARMENV_EXPLOIT_MAX_TENSORS 128
+typedef struct ArmEnvPopExploitArgs {
+  int32_t device, members, tensors, reserved;
+  const int32_t *src;    /* HOST [members]: member p becomes a copy of member src[p]; src[p] == p keeps it */
+  float *const *base;    /* HOST [tensors]: member 0's array of each stack [P][...] (device pointers) */
+  const int64_t *elems;  /* HOST [tensors]: floats per member of that stack = its member stride */
+} ArmEnvPopExploitArgs;
+int armenv_pop_exploit(const ArmEnvPopExploitArgs *args, void *stream);
 
 /* Measurement aid (bench.py's roofline.valu.one_wave_per_simd; no reference counterpart): the interval at which SIMDs issue
  * independent 64-lane v_fma_f64 (precision 64) / v_fma_f32 (32) instructions when every SIMD of `device` holds
