@@ -1,22 +1,15 @@
-"""What tests/test_gpu_daddpg_pop.py and tests/test_gpu_datd3_pop.py share: the populations of the two-actor agents (kind "daddpg",
-"datd3" or "darc") on cuda:0 and the checks that do not depend on the agent.  The oracle is the single-learner update: member p of
-a population update equals the single entry point on member p's tensors BIT FOR BIT -- no tolerance anywhere."""
+"""What the GPU tests of the population updates share (tests/test_gpu_td3_pop.py, test_gpu_daddpg_pop.py, test_gpu_datd3_pop.py,
+test_gpu_pop_hyper.py, test_gpu_pbt.py): the populations of the four agents (kind "td3", "daddpg", "datd3" or "darc") on cuda:0 and
+the checks that do not depend on the agent.  The oracle is the single-learner update: member p of a population update equals the
+single entry point on member p's tensors BIT FOR BIT -- no tolerance anywhere."""
 import ctypes as C
 
 import torch
 
+from learner_host import classes  # noqa: F401  ((population class, single class, the C entry points' stem) of a kind)
+
 DEV = "cuda:0"
 PAD, CANARY = 64, 12345.0
-
-
-def classes(kind):
-    """(population class, single class, the C entry points' stem)"""
-    from armenv.fused_daddpg import FusedDADDPG
-    from armenv.fused_daddpg_pop import FusedDADDPGPopulation
-    from armenv.fused_datd3 import FusedDARC, FusedDATD3
-    from armenv.fused_datd3_pop import FusedDARCPopulation, FusedDATD3Population
-    return dict(daddpg=(FusedDADDPGPopulation, FusedDADDPG, "daddpg"), datd3=(FusedDATD3Population, FusedDATD3, "datd3"),
-                darc=(FusedDARCPopulation, FusedDARC, "datd3"))[kind]
 
 
 def generator(seed):
@@ -47,7 +40,9 @@ def randomise(pop, gen):
             t.copy_(x.abs() * 1e-3 if name.endswith("_v") else x * (0.01 if name.endswith("_m") else 1.0))
 
 
-MID_RUN = dict(daddpg=dict(total_it=5, critic_step=5, actor1_step=2, actor2_step=3),
+# TD3 (policy_freq 3) steps its actor at total_it 6 and 9: the second and the fifth train from here
+MID_RUN = dict(td3=dict(total_it=4, critic_step=4, actor_step=1),
+               daddpg=dict(total_it=5, critic_step=5, actor1_step=2, actor2_step=3),
                datd3=dict(total_it=6, actor1_step=3, critic1_step=3, actor2_step=3, critic2_step=3))
 MID_RUN["darc"] = MID_RUN["datd3"]
 
@@ -67,7 +62,12 @@ def state(pop, p):
 
 
 def stack_names(pop, k):
-    """(stacks an update of actor / critic k writes, stacks it must leave alone)"""
+    """(stacks an update writes, stacks it must leave alone); k: the actor / critic that the update steps, TD3: whether it takes the
+    actor step"""
+    if "q1" in pop.stacks:                # TD3: the actor, its moments and all three targets move with the actor step only
+        with_actor = ["actor", "actor_m", "actor_v", "target_actor", "target_q1", "target_q2"]
+        written = ["q1", "q2", "q1_m", "q1_v", "q2_m", "q2_v"] + (with_actor if k else [])
+        return written, [] if k else with_actor
     other = 3 - k
     if "critic" in pop.stacks:            # DADDPG: one critic, its target moves only with actor 2
         written = ["actor%d" % k, "target_actor%d" % k, "actor%d_m" % k, "actor%d_v" % k, "critic", "critic_m", "critic_v"]
@@ -84,7 +84,8 @@ def train(kind, learner, b, noise=None):
     """one `train` of a population or a single learner; the losses as a list of tensors"""
     if kind == "daddpg":
         return [learner.train(b)]
-    return list(learner.train(b, noise=noise))
+    losses = learner.train(b, noise=noise)
+    return [losses] if kind == "td3" else list(losses)
 
 
 def run(kind, P, B, D, batches, noises, seed_gen=3, **kw):
@@ -94,17 +95,37 @@ def run(kind, P, B, D, batches, noises, seed_gen=3, **kw):
 
 
 def train_noises(kind, gen, P, B, count):
-    """`count` train calls' given noise: None for DADDPG, a pair per call for DATD3 / DARC"""
-    return [None if kind == "daddpg" else (noise_for(gen, P, B), noise_for(gen, P, B)) for _ in range(count)]
+    """`count` train calls' given noise: None for DADDPG, one tensor per call for TD3, a pair per call for DATD3 / DARC"""
+    def one():
+        if kind == "daddpg":
+            return None
+        return noise_for(gen, P, B) if kind == "td3" else (noise_for(gen, P, B), noise_for(gen, P, B))
+    return [one() for _ in range(count)]
+
+
+def updates(kind):
+    """what one C call is asked for, in turn: TD3 without and with the actor step, the others actor / critic 1 then 2"""
+    return (0, 1) if kind == "td3" else (1, 2)
+
+
+def set_update(one, kind, k, draw, noise=None):
+    """the fields of `one` that name the update: which one, and (where the agent has noise) its draw and its given noise"""
+    if kind == "td3":
+        one.with_actor = k
+    else:
+        one.update_actor = k
+    if kind != "daddpg":
+        one.draw = draw
+        one.noise_dev = noise.data_ptr() if noise is not None else None
 
 
 def check_members_do_not_leak(kind):
-    """Two train calls twice, the second time with member 1's batch perturbed: members 0 and 2 are bit-identical to the first run
-    and member 1 is not."""
+    """Three train calls (TD3: the second with the actor step) twice, the second time with member 1's batch perturbed: members 0 and
+    2 are bit-identical to the first run and member 1 is not."""
     P, B, D = 3, 257, 6
     gen = generator(21)
-    batches = [batch(gen, P, B, D) for _ in range(2)]
-    noises = train_noises(kind, gen, P, B, 2)
+    batches = [batch(gen, P, B, D) for _ in range(3)]
+    noises = train_noises(kind, gen, P, B, 3)
     a, la = run(kind, P, B, D, batches, noises)
     perturbed = [{k: v.clone() for k, v in b.items()} for b in batches]
     for b in perturbed:
@@ -120,64 +141,55 @@ def check_members_do_not_leak(kind):
 
 
 def check_canaries(kind):
-    """A canary of 64 floats on both sides of every stack, of every batch array, of the loss and of the workspace survives two
-    updates (both actors / critics stepped once)."""
+    """A canary of 64 floats on both sides of every stack, of the workspace, and of every batch array and the loss of each of three
+    updates survives them (TD3: the second with the actor step; the others: actor / critic 1, 2, 1)."""
     from armenv import _lib as L
     P, B, D = 3, 257, 9
     gen = generator(31)
     pop = population(kind, P, D, gen)
     stem = classes(kind)[2]
+    bufs = []
 
     def padded(t):
         """a copy of t inside a buffer with PAD canary floats (or bytes, for uint8) before and after it"""
         buf = torch.full((t.numel() + 2 * PAD,), CANARY if t.dtype == torch.float32 else 77, dtype=t.dtype, device=DEV)
         inner = buf[PAD:PAD + t.numel()].view(t.shape)
         inner.copy_(t)
-        return buf, inner
+        bufs.append(buf)
+        return inner
 
-    bufs = []
     for name in list(pop.stacks):
-        for k, t in enumerate(pop.stacks[name]):
-            buf, inner = padded(t)
-            bufs.append(buf)
-            pop.stacks[name][k] = inner
+        pop.stacks[name] = [padded(t) for t in pop.stacks[name]]
     lib = L.load()
     ws_bytes = getattr(lib, "armenv_%s_pop_workspace_bytes" % stem)(D, 256, B, P)
-    ws_buf = torch.full((ws_bytes // 4 + 2 * PAD,), CANARY, device=DEV)
-    bufs.append(ws_buf)
-    ws = ws_buf[PAD:PAD + ws_bytes // 4].view(torch.uint8)
+    ws = padded(torch.zeros(ws_bytes // 4, device=DEV)).view(torch.uint8)
     assert ws.numel() == ws_bytes and ws.data_ptr() % 16 == 0
-    loss_buf, loss = padded(torch.zeros(P, device=DEV))
-    bufs.append(loss_buf)
     before = [t.clone() for t in state(pop, 1)]
-    held = {}
-    for k, t in batch(gen, P, B, D).items():
-        buf, inner = padded(t)
-        bufs.append(buf)
-        held[k] = inner
     pa = pop._static_args()
     one = pa.one
     one.batch, one.critic_step, one.actor_step = B, 4, 4
-    one.states_dev, one.actions_dev, one.next_states_dev = (held[k].data_ptr() for k in ("states", "actions", "next_states"))
-    one.rewards_dev, one.dones_dev, one.loss_dev = held["rewards"].data_ptr(), held["dones"].data_ptr(), loss.data_ptr()
     one.workspace_dev, one.workspace_bytes = ws.data_ptr(), ws.numel()
     stream = C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-    for k in (1, 2):
-        one.update_actor = k
-        if kind != "daddpg":
-            one.draw = 6 + k
+    losses = []
+    for i, k in enumerate(updates(kind) + updates(kind)[:1]):
+        held = {name: padded(t) for name, t in batch(gen, P, B, D).items()}
+        losses.append(padded(torch.zeros(P, device=DEV)))
+        one.states_dev, one.actions_dev, one.next_states_dev = (held[n].data_ptr() for n in ("states", "actions", "next_states"))
+        one.rewards_dev, one.dones_dev, one.loss_dev = held["rewards"].data_ptr(), held["dones"].data_ptr(), losses[-1].data_ptr()
+        set_update(one, kind, k, 7 + i)
         L.check(getattr(lib, "armenv_%s_pop_update" % stem)(C.byref(pa), stream))
     torch.cuda.synchronize(DEV)
+    assert len(bufs) == 6 * len(pop.stacks) + 1 + 3 * 6
     for buf in bufs:
         edge = torch.cat([buf[:PAD], buf[-PAD:]])
         assert bool((edge == (CANARY if buf.dtype == torch.float32 else 77)).all())
-    assert bool(torch.isfinite(loss).all()) and bool((loss > 0).all())
+    assert all(bool(torch.isfinite(loss).all()) and bool((loss > 0).all()) for loss in losses)
     assert not any(torch.equal(x, y) for x, y in zip(before[:6], state(pop, 1)[:6]))      # the update did run on the padded stacks
 
 
-def prepared_call(kind, P, B, D, b, noise, seed_gen, updates=(1, 2), use_pop=True):
+def prepared_call(kind, P, B, D, b, noise, seed_gen, use_pop=True):
     """(population, call, loss): `call()` enqueues armenv_<algo>_pop_update (or, P = 1 and use_pop False, the single entry point on
-    the very same argument struct `one`) once per entry of `updates` with fixed step numbers, on the current stream"""
+    the very same argument struct `one`) once per entry of updates(kind) with fixed step numbers, on the current stream"""
     from armenv import _lib as L
     lib = L.load()
     stem = classes(kind)[2]
@@ -186,7 +198,7 @@ def prepared_call(kind, P, B, D, b, noise, seed_gen, updates=(1, 2), use_pop=Tru
     one = pa.one
     n = getattr(lib, "armenv_%s_pop_workspace_bytes" % stem)(D, 256, B, P)
     ws = torch.empty(n, dtype=torch.uint8, device=DEV)
-    loss = torch.zeros(len(updates), P, device=DEV)
+    loss = torch.zeros(len(updates(kind)), P, device=DEV)
     one.batch, one.critic_step, one.actor_step = B, 5, 4
     one.states_dev, one.actions_dev, one.next_states_dev = (b[k].data_ptr() for k in ("states", "actions", "next_states"))
     one.rewards_dev, one.dones_dev = b["rewards"].data_ptr(), b["dones"].data_ptr()
@@ -194,18 +206,16 @@ def prepared_call(kind, P, B, D, b, noise, seed_gen, updates=(1, 2), use_pop=Tru
     fn = getattr(lib, "armenv_%s_pop_update" % stem) if use_pop else getattr(lib, "armenv_%s_update" % stem)
 
     def call():
-        for i, k in enumerate(updates):
-            one.update_actor, one.loss_dev = k, loss[i].data_ptr()
-            if kind != "daddpg":
-                one.draw = 7 + i
-                one.noise_dev = noise[i].data_ptr() if noise is not None else None
+        for i, k in enumerate(updates(kind)):
+            one.loss_dev = loss[i].data_ptr()
+            set_update(one, kind, k, 7 + i, None if noise is None else noise[i])
             L.check(fn(C.byref(pa) if use_pop else C.byref(one), C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)))
     return pop, call, loss, (ws, pa)
 
 
 def check_one_member_equals_the_single_update_on_the_same_tensors(kind):
     """P = 1: the population entry point and the single entry point called on THE SAME tensors (a copy of the state, the very same
-    argument struct as `one`) give the same bits, for k = 1 and k = 2."""
+    argument struct as `one`) give the same bits, for both entries of updates(kind)."""
     gen = generator(41)
     B, D = 257, 6
     b = batch(gen, 1, B, D)
@@ -218,11 +228,11 @@ def check_one_member_equals_the_single_update_on_the_same_tensors(kind):
 
 
 def check_determinism(kind):
-    """Three populations from the same state, three train calls on the same batches with the in-kernel noise, two on the default
+    """Three populations from the same state, six train calls on the same batches with the in-kernel noise, two on the default
     stream and one on a side stream: all tensors and losses are bitwise equal."""
     P, B, D = 3, 257, 6
     gen = generator(51)
-    batches = [batch(gen, P, B, D) for _ in range(3)]
+    batches = [batch(gen, P, B, D) for _ in range(6)]
     pops = [population(kind, P, D, generator(52)) for _ in range(3)]
     side = torch.cuda.Stream(device=DEV)
     losses = [[], [], []]
@@ -241,18 +251,16 @@ def check_determinism(kind):
 
 
 def check_graph_capture(kind):
-    """One `train`'s calls (DADDPG: one update, with the target critic's soft update; DATD3 / DARC: k = 1 then k = 2) captured into
-    a torch.cuda.graph on one stream and replayed three times equal three direct runs with the same arguments, bit for bit: the call
-    only enqueues kernels, one serial chain."""
+    """One call per entry of updates(kind), with given noise, captured into a torch.cuda.graph on one stream and replayed three times
+    equals three direct runs with the same arguments, bit for bit: the call only enqueues kernels, one serial chain."""
     P, B, D = 3, 257, 6
     gen = generator(61)
     b = batch(gen, P, B, D)
-    updates = (2,) if kind == "daddpg" else (1, 2)
-    noise = None if kind == "daddpg" else [noise_for(gen, P, B) for _ in updates]
-    direct, call_d, loss_d, _kd = prepared_call(kind, P, B, D, b, noise, 62, updates)
+    noise = None if kind == "daddpg" else [noise_for(gen, P, B) for _ in updates(kind)]
+    direct, call_d, loss_d, _kd = prepared_call(kind, P, B, D, b, noise, 62)
     for _ in range(3):
         call_d()
-    graphed, call_g, loss_g, _kg = prepared_call(kind, P, B, D, b, noise, 62, updates)
+    graphed, call_g, loss_g, _kg = prepared_call(kind, P, B, D, b, noise, 62)
     torch.cuda.synchronize(DEV)
     before = [t.clone() for p in range(P) for t in state(graphed, p)]
     g = torch.cuda.CUDAGraph()
@@ -266,20 +274,21 @@ def check_graph_capture(kind):
     for p in range(P):
         assert all(torch.equal(x, y) for x, y in zip(state(direct, p), state(graphed, p))), p
     assert torch.equal(loss_d, loss_g)
-    changed = "actor2" if kind == "daddpg" else "actor1"
-    index = 6 * graphed._NETS.index(changed)
-    assert not torch.equal(before[index], state(graphed, 0)[index])
+    assert not torch.equal(before[0], state(graphed, 0)[0])                # the first actor's W1: every kind's updates step it
 
 
 def check_zero_learning_rates(kind):
+    """Three train calls (TD3: the second with the actor step) under zero rates and tau: the nets are bitwise what they were"""
     P, B, D = 3, 64, 6
     gen = generator(71)
     pop = population(kind, P, D, gen, actor_lr=0.0, critic_lr=0.0, tau=0.0)
     n_nets = 6 * len(pop._NETS)
     before = [[t.clone() for t in state(pop, p)[:n_nets]] for p in range(P)]          # the nets; the moments do move
-    for _ in range(2):
+    for _ in range(3):
         losses = train(kind, pop, batch(gen, P, B, D))
     assert all(bool(torch.isfinite(x).all()) for x in losses)
+    assert all(getattr(pop, name) > value for name, value in MID_RUN[kind].items())   # every optimiser stepped ...
+    assert kind != "td3" or pop.actor_step == 2                                        # ... TD3's actor once
     for p in range(P):
         assert all(torch.equal(x, y) for x, y in zip(before[p], state(pop, p)[:n_nets])), p
 
@@ -290,13 +299,14 @@ def check_round_trip(kind):
     pop = population(kind, 2, 6, gen)
     torch.manual_seed(4)
     single = Single(6, 3, 0.7, device=DEV) if kind == "daddpg" else Single(6, 3, 0.7, device=DEV, seed=3)
-    for _ in range(3):
+    for _ in range(4):
         train(kind, single, member_batch(batch(gen, 1, 64, 6), 0))
     names = Pop._COUNTERS
     want = tuple(getattr(single, n) for n in names)
-    assert want[0] == (3 if kind == "daddpg" else 6)
+    assert want[0] == (4 if kind in ("td3", "daddpg") else 8) and all(want)
     pop.load_member(1, single)
     assert tuple(getattr(pop, n) for n in names) == want
+    assert kind != "td3" or (pop.total_it, pop.critic_step, pop.actor_step) == (4, 4, 1)
     assert all(torch.equal(x, y) for x, y in zip(state(pop, 1), Pop._single_state(single)))
     back = pop.export_member(1)
     assert type(back) is Single and tuple(getattr(back, n) for n in names) == want

@@ -355,6 +355,26 @@ def state_from(actor, critic, target_actor, target_critic, actor_m, actor_v, cri
                 actor_step=int(actor_step), critic_step=int(critic_step))
 
 
+def random_batch(gen, B, D, done_p=0.3):
+    """a float64 batch on the CPU, for the comparisons with float64 autograd"""
+    return dict(states=torch.rand(B, D, generator=gen, dtype=torch.float64),
+                actions=torch.rand(B, 3, generator=gen, dtype=torch.float64) * 0.5 - 0.25,
+                next_states=torch.rand(B, D, generator=gen, dtype=torch.float64),
+                rewards=torch.rand(B, generator=gen, dtype=torch.float64) - 0.5,
+                dones=(torch.rand(B, generator=gen, dtype=torch.float64) < done_p).to(torch.float64))
+
+
+def adam_state(net, opt):
+    """(m, v, step) of torch.optim.Adam `opt` over net's parameters; zeros before its first step"""
+    m, v, step = [], [], 0
+    for p in net.parameters():
+        s = opt.state.get(p, {})
+        m.append(s["exp_avg"] if "exp_avg" in s else torch.zeros_like(p))
+        v.append(s["exp_avg_sq"] if "exp_avg_sq" in s else torch.zeros_like(p))
+        step = int(s["step"]) if "step" in s else 0
+    return m, v, step
+
+
 def advance(state, out, with_actor):
     """the state after the update `out` = td3_update(state, ...)"""
     nxt = dict(state, critic=out["critic"], critic_m=out["critic_m"], critic_v=out["critic_v"], critic_step=state["critic_step"] + 1)

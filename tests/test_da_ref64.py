@@ -10,6 +10,7 @@ from conftest import golden_npz
 import da_cases as K
 import da_ref64 as R
 from datd3_golden import KEYS, expected_losses, load_train_fixture
+from td3_ref64 import adam_state, random_batch
 
 HP_GOLDEN = dict(K.HP, beta1=0.9)
 # against autograd: a q_weight whose 1 - q_weight is an f32 value, so that the kernel's two f32 weights ARE the torch learner's
@@ -93,25 +94,10 @@ def test_datd3_reference_reproduces_the_golden_updates(agent):
 
 # ---- equality with float64 autograd ----
 
-def _batch(gen, B, D, done_p=0.3):
-    return dict(states=torch.rand(B, D, generator=gen, dtype=torch.float64),
-                actions=torch.rand(B, 3, generator=gen, dtype=torch.float64) * 0.5 - 0.25,
-                next_states=torch.rand(B, D, generator=gen, dtype=torch.float64),
-                rewards=torch.rand(B, generator=gen, dtype=torch.float64) - 0.5,
-                dones=(torch.rand(B, generator=gen, dtype=torch.float64) < done_p).to(torch.float64))
-
-
 def _torch_state(agent, t):
-    moments, steps = {}, {}
-    for name in R.LEARNING[agent]:
-        opt, m, v, step = getattr(t, name + "_opt"), [], [], 0
-        for p in getattr(t, name).parameters():
-            s = opt.state.get(p, {})
-            m.append(s["exp_avg"] if "exp_avg" in s else torch.zeros_like(p))
-            v.append(s["exp_avg_sq"] if "exp_avg_sq" in s else torch.zeros_like(p))
-            step = int(s["step"]) if "step" in s else 0
-        moments[name], steps[name] = (m, v), step
-    return R.state_from(agent, {n: getattr(t, n) for n in R.NETS[agent]}, moments, steps)
+    adam = {name: adam_state(getattr(t, name), getattr(t, name + "_opt")) for name in R.LEARNING[agent]}
+    return R.state_from(agent, {n: getattr(t, n) for n in R.NETS[agent]}, {n: mvs[:2] for n, mvs in adam.items()},
+                        {n: mvs[2] for n, mvs in adam.items()})
 
 
 _AUTOGRAD = {}
@@ -149,10 +135,10 @@ def _autograd_case(agent, B, D, k, seed, hp, gain=1.0):
         args = (batch["states"], batch["actions"], batch["rewards"].view(-1, 1), batch["next_states"], batch["dones"].view(-1, 1), kk == 1)
         return float(t._update(*args) if agent == "daddpg" else t._update(*args, noise))
     for kk in (1, 2):
-        update(_batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64), kk)
+        update(random_batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64), kk)
     st = _torch_state(agent, t)
     assert all(st[n + "_step"] == 1 for n in R.LEARNING[agent] if n != "critic") and st.get("critic_step", 2) == 2
-    batch, noise = _batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64)
+    batch, noise = random_batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64)
     loss = float(update(batch, noise, k))
     after = _torch_state(agent, t)
     grads = {n: [p.grad.detach().clone() for p in getattr(t, n).parameters()] for n in R.LEARNING[agent]}

@@ -3,23 +3,12 @@ tensors an update may touch, DARC's target arithmetic; and the fused update's ho
 ctypes struct agrees with the header, every argument is validated before any HIP call, the workspace query, the new kernels in the
 built code object, and the training loop's learner choices."""
 import ctypes as C
-import os
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from datd3_golden import NETS, batch, expected_losses, load_train_fixture
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
-import isa  # noqa: E402
-
-HEADER_DIR = os.path.join(ROOT, "include")
-MOMENTS = tuple(n + mv for n in NETS[:4] for mv in ("_m", "_v"))
-ALL_NETS = NETS + MOMENTS
+from learner_host import DATD3_NETS as ALL_NETS, REFUSALS, ctypes_layout, fake_args, header_layout, learner_kernels  # noqa: F401
 
 
 @pytest.mark.parametrize("algo", ["datd3", "darc"])
@@ -121,118 +110,24 @@ def test_darc_target_is_the_rounded_mix_not_T():
         assert float((p - q).detach().abs().max()) <= 2.1e-3          # one Adam step moves an element by at most lr, either way
 
 
-def _ctypes_layout(struct, prefix=""):
-    """[(C member path, offset)] of every scalar member of a ctypes struct, nested structs flattened"""
-    out = []
-    for name, typ in struct._fields_:
-        off = getattr(struct, name).offset
-        if isinstance(typ, type) and issubclass(typ, C.Structure):
-            out += [(f"{prefix}{name}.{k}", off + o) for k, o in _ctypes_layout(typ)]
-        else:
-            out.append((prefix + name, off))
-    return out
-
-
 def test_datd3_struct_layout_matches_the_header():
     from armenv import _lib as L
-    members = _ctypes_layout(L.ArmEnvDatd3Args)
-    assert {m.split(".")[0] for m, _ in members} >= set(ALL_NETS) | {
+    members = ctypes_layout(L.ArmEnvDatd3Args)
+    assert ALL_NETS[:8] == NETS and {m.split(".")[0] for m, _ in members} >= set(ALL_NETS) | {
         "update_actor", "darc", "q_weight", "regularization_weight", "policy_noise", "noise_clip", "seed", "draw", "noise_dev",
         "critic_step", "actor_step", "loss_dev"}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "armenv.h"', "int main(void) {",
-             '  printf("%zu %d\\n", sizeof(ArmEnvDatd3Args), ARMENV_ABI_VERSION);']
-    lines += ['  printf("%%zu\\n", offsetof(ArmEnvDatd3Args, %s));' % m for m, _ in members]
-    lines += ["  return 0;", "}"]
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        with open(src, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
-        subprocess.run(["gcc", "-std=c99", "-Wall", "-I", HEADER_DIR, "-o", exe, src], check=True)
-        out = subprocess.run([exe], check=True, stdout=subprocess.PIPE, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(L.ArmEnvDatd3Args) and int(out[1]) == L.ABI_VERSION == 8
-    assert [int(x) for x in out[2:]] == [o for _, o in members], members
+    sizes, offsets = header_layout(L.ArmEnvDatd3Args, extra=("ARMENV_ABI_VERSION",))
+    assert sizes[0] == C.sizeof(L.ArmEnvDatd3Args) and sizes[1] == L.ABI_VERSION == 8
+    assert offsets == [o for _, o in members], members
 
 
-def _args(B=64, D=6, darc=1):
-    """Arguments that pass every check but the one a test breaks: fake (never dereferenced) 16-byte aligned device pointers.
-    NOT to be passed unmodified -- a valid set would be enqueued."""
-    from armenv import _lib as L
-    a = L.ArmEnvDatd3Args()
-    a.device, a.state_dim, a.action_dim, a.hidden_dim, a.batch = 0, D, 3, 256, B
-    a.action_bound, a.gamma, a.tau, a.policy_noise, a.noise_clip = 0.7, 0.98, 0.005, 0.2, 0.5
-    a.actor_lr, a.critic_lr, a.beta1, a.beta2, a.eps = 1e-3, 1e-3, 0.9, 0.999, 1e-8
-    a.q_weight, a.regularization_weight, a.darc = 0.2, 0.005, darc
-    a.critic_step, a.actor_step, a.update_actor = 1, 1, 2
-    addr = [0x10000]
-
-    def ptr():
-        addr[0] += 0x1000
-        return addr[0]
-    for net in ALL_NETS:
-        m = getattr(a, net)
-        for k in ("W1", "b1", "W2", "b2", "W3", "b3"):
-            setattr(m, k, ptr())
-    for k in ("states_dev", "actions_dev", "next_states_dev", "rewards_dev", "dones_dev", "workspace_dev"):
-        setattr(a, k, ptr())
-    a.workspace_bytes = L.load().armenv_datd3_workspace_bytes(D, 256, B)
-    assert a.workspace_bytes > 0
-    return a
-
-
-def _breaks(mutate):
+@pytest.mark.parametrize("field,mutate", REFUSALS["datd3"])
+def test_datd3_bad_arguments_are_refused_before_any_device_call(field, mutate):
     from armenv import _lib as L
     lib = L.load()
-    a = _args()
+    a = fake_args("darc")
     mutate(a)
-    rc = lib.armenv_datd3_update(C.byref(a), None)
-    return rc, lib.armenv_last_error().decode()
-
-
-def _null(net, key):
-    return lambda a: setattr(getattr(a, net), key, None)
-
-
-@pytest.mark.parametrize("field,mutate", [
-    ("batch", lambda a: setattr(a, "batch", 0)),
-    ("batch", lambda a: setattr(a, "batch", (1 << 20) + 1)),
-    ("hidden_dim", lambda a: setattr(a, "hidden_dim", 128)),
-    ("state_dim", lambda a: setattr(a, "state_dim", 0)),
-    ("state_dim", lambda a: setattr(a, "state_dim", 13)),
-    ("action_dim", lambda a: setattr(a, "action_dim", 2)),
-    ("update_actor", lambda a: setattr(a, "update_actor", 0)),
-    ("update_actor", lambda a: setattr(a, "update_actor", 3)),
-    ("darc", lambda a: setattr(a, "darc", 2)),
-    ("darc", lambda a: setattr(a, "darc", -1)),
-    ("critic_step", lambda a: setattr(a, "critic_step", 0)),
-    ("actor_step", lambda a: setattr(a, "actor_step", 0)),
-    ("action_bound", lambda a: setattr(a, "action_bound", 0.0)),
-    ("gamma", lambda a: setattr(a, "gamma", float("nan"))),
-    ("tau", lambda a: setattr(a, "tau", 1.5)),
-    ("policy_noise", lambda a: setattr(a, "policy_noise", -0.1)),
-    ("noise_clip", lambda a: setattr(a, "noise_clip", float("inf"))),
-    ("actor_lr", lambda a: setattr(a, "actor_lr", -1e-3)),
-    ("critic_lr", lambda a: setattr(a, "critic_lr", float("nan"))),
-    ("beta1", lambda a: setattr(a, "beta1", 1.0)),
-    ("beta2", lambda a: setattr(a, "beta2", -0.1)),
-    ("eps", lambda a: setattr(a, "eps", 0.0)),
-    ("q_weight", lambda a: setattr(a, "q_weight", 1.5)),
-    ("q_weight", lambda a: setattr(a, "q_weight", -0.1)),
-    ("regularization_weight", lambda a: setattr(a, "regularization_weight", -0.005)),
-    ("regularization_weight", lambda a: setattr(a, "regularization_weight", float("nan"))),
-] + [(net, _null(net, key)) for net, key in zip(ALL_NETS, ("W1", "b1", "W2", "b2", "W3", "b3") * 3)] + [
-    ("target_critic2", lambda a: setattr(a.target_critic2, "b1", a.target_critic2.b1 + 4)),      # misaligned
-    ("critic1_v", lambda a: setattr(a.critic1_v, "W1", a.critic1_v.W1 + 8)),                    # misaligned
-    ("states_dev", lambda a: setattr(a, "states_dev", None)),
-    ("actions_dev", lambda a: setattr(a, "actions_dev", None)),
-    ("next_states_dev", lambda a: setattr(a, "next_states_dev", None)),
-    ("rewards_dev", lambda a: setattr(a, "rewards_dev", None)),
-    ("dones_dev", lambda a: setattr(a, "dones_dev", None)),
-    ("workspace_dev", lambda a: setattr(a, "workspace_dev", None)),
-    ("workspace_dev", lambda a: setattr(a, "workspace_dev", a.workspace_dev + 4)),
-    ("workspace_bytes", lambda a: setattr(a, "workspace_bytes", a.workspace_bytes - 1)),
-])
-def test_datd3_bad_arguments_are_refused_before_any_device_call(field, mutate):
-    rc, msg = _breaks(mutate)
+    rc, msg = lib.armenv_datd3_update(C.byref(a), None), lib.armenv_last_error().decode()
     assert rc == -1, (rc, msg)                       # ARMENV_EINVAL, not ENODEV: nothing touched the device
     assert field in msg and "armenv_datd3_update" in msg, msg
 
@@ -262,16 +157,6 @@ def test_datd3_workspace_size_queries():
         assert q(6, 256, B) >= 4 * (16 * B * H + S * actor_slice + 2 * B), B
         assert q(6, 256, B) >= lib.armenv_daddpg_workspace_bytes(6, 256, B) + 4 * (2 * B * H + 2 * B), B
         assert q(9, 256, B) == q(6, 256, B)
-
-
-@pytest.fixture(scope="module")
-def learner_kernels():
-    if not os.path.exists(isa.LIB):
-        pytest.skip("libarmenv.so is not built")
-    if not os.path.exists(os.path.join(isa.LLVM, "llvm-objdump")):
-        pytest.skip("the ROCm LLVM tools (llvm-objdump, llvm-readelf) are not installed")
-    rows = [r for r in isa.all_kernels() if "armenv::learner::" in r[1]]
-    return {dm.split("armenv::learner::")[1].split("(")[0]: (md, ins) for _, dm, md, ins in rows}
 
 
 def test_datd3_kernels_are_in_the_code_object(learner_kernels):

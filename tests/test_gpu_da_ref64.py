@@ -10,7 +10,6 @@ checks the same inputs for ambiguity without a GPU.  C is one constant per kind 
 (profiles/da_ref64_errors.txt records the largest measured ratios; each C is at most 8x the largest, and TD3's value where that
 already satisfies the rule)."""
 import copy
-import json
 import os
 
 import numpy as np
@@ -19,22 +18,20 @@ import torch
 
 import da_cases as K
 import da_ref64 as R
+from learner_gpu import DEV, Bounds, f64 as _f64
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 C = dict(critic_grad=1.0, actor_grad=0.5, loss=0.05, adam=16.0, noise=0.015)
-RATIOS = {}                      # (kind, case) -> largest |got - ref| - allowance, in units of 2^-24 M
+BOUNDS = Bounds(C, K.AMB_MAX)
+_check, _grad_failures, _adam_failures = BOUNDS.check, BOUNDS.grad_failures, BOUNDS.adam_failures
+_ambiguity_is_rare = BOUNDS.ambiguity_is_rare
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _ratio_log():
     """ARMENV_DA_REF64_RATIOS=<path>: write the largest measured ratio per kind and case there (calibration of C)"""
     yield
-    path = os.environ.get("ARMENV_DA_REF64_RATIOS")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as fh:
-            json.dump({"%s|%s" % k: v for k, v in sorted(RATIOS.items())}, fh, indent=1)
+    BOUNDS.write(os.environ.get("ARMENV_DA_REF64_RATIOS"))
 
 
 def _critic_net(c):
@@ -66,10 +63,6 @@ def _make(c, built, beta1=None, seed=0):
     if agent == "daddpg":
         f.total_it = 1 if c["k"] == 1 else 0          # update n steps actor 1 when n is even
     return f
-
-
-def _f64(xs):
-    return [t.detach().to(torch.float64) for t in (xs.parameters() if hasattr(xs, "parameters") else xs)]
 
 
 def _snapshot(f, agent):
@@ -116,43 +109,6 @@ def _unowned_changes(c, built, got):
     assert len(before) - len(owned) == (4 if c["agent"] == "daddpg" else 8) + (1 if c["agent"] == "daddpg" and c["k"] == 1 else 0)
     return [name for name, ts in before.items() if name not in owned
             and not all(torch.equal(a.to(DEV), b) for a, b in zip(ts, got["all"][name]))]
-
-
-def _check(kind, case, got, ref, mag, allow=None, record=True):
-    """number of elements beyond C[kind] 2^-24 mag + allow; `record`: keep the largest ratio for the calibration log"""
-    n, ratio = R.bad_elements(got, ref, mag, torch.zeros_like(mag) if allow is None else allow, C[kind])
-    if record:
-        RATIOS[(kind, case)] = max(RATIOS.get((kind, case), 0.0), ratio)
-    return n
-
-
-def _grad_failures(case, got, out, record=True):
-    """quantities whose kernel gradient / loss lies beyond the bound around the reference `out` (beta1 = 0: m is the gradient)"""
-    bad = []
-    lt = lambda x: torch.tensor([x], dtype=torch.float64)
-    if _check("loss", case, lt(got["loss"]), lt(out["loss"]), lt(out["loss_mag"]), record=record):
-        bad.append("loss")
-    for side in ("critic", "actor"):
-        for k, g in enumerate(got[side + "_m"]):
-            if _check(side + "_grad", case, g, out[side + "_grad"][k], out[side + "_grad_mag"][k], out[side + "_grad_allow"][k], record):
-                bad.append("%s_grad%d" % (side, k))
-    return bad
-
-
-def _adam_failures(case, got, out, sides=("critic", "actor"), record=True):
-    """Adam-stepped parameters, moments and soft-updated targets beyond C_adam 2^-24 of their magnitudes"""
-    bad = []
-    for side in sides:
-        for name in (side, side + "_m", side + "_v", "target_" + side):
-            for k, t in enumerate(got[name]):
-                if _check("adam", case, t, out[name][k], out[name + "_mag"][k], record=record):
-                    bad.append("%s%d" % (name, k))
-    return bad
-
-
-def _ambiguity_is_rare(out):
-    assert out["ambiguous"] <= K.AMB_MAX * out["units"], (out["ambiguous"], out["units"])
-    RATIOS[("ambiguous_fraction", "max")] = max(RATIOS.get(("ambiguous_fraction", "max"), 0.0), out["ambiguous"] / out["units"])
 
 
 def _against_float64(c):

@@ -2,41 +2,22 @@
 armenv.daddpg.DADDPG, which restates DADDPG_MLP.update (the reference's algo/DADDPG/DADDPG_mlp.py:117-171): the reference's golden
 run (G16), the alternation of the two actors bit for bit, gradients against float64 autograd, free-running agreement, batch / state
 sizes, determinism across runs and streams, and the training loop with learner="fused"."""
-import copy
 import json
 
 import numpy as np
 import pytest
 import torch
 
+import learner_gpu as G
 from conftest import golden_npz
-from test_gpu_td3_fused import _assert_grads
+from learner_gpu import DEV, assert_grads as _assert_grads, batch as _batch, f64_net as _f64, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _batch(gen, B, D=6):
-    return dict(states=torch.rand(B, D, device=DEV, generator=gen), actions=torch.rand(B, 3, device=DEV, generator=gen) * 1.4 - 0.7,
-                next_states=torch.rand(B, D, device=DEV, generator=gen), rewards=torch.rand(B, device=DEV, generator=gen) - 0.5,
-                dones=(torch.rand(B, device=DEV, generator=gen) < 0.1).to(torch.uint8))
+NETS = ("actor1", "actor2", "critic", "target_actor1", "target_actor2", "target_critic")
 
 
 def _state(f):
-    """every tensor a fused update may write, by name"""
-    out = {}
-    for name in ("actor1", "actor2", "critic", "target_actor1", "target_actor2", "target_critic"):
-        for k, v in getattr(f, name).state_dict().items():
-            out[f"{name}.{k}"] = v.clone()
-    for name in ("actor1", "actor2", "critic"):
-        for mv in ("_m", "_v"):
-            for i, t in enumerate(getattr(f, name + mv)):
-                out[f"{name}{mv}.{i}"] = t.clone()
-    return out
+    return G.state(f, NETS, NETS[:3])
 
 
 def test_fused_daddpg_reproduces_the_golden_updates():
@@ -95,10 +76,6 @@ def test_fused_daddpg_alternates_the_actors_exactly():
             if k.startswith(moved + ("critic.", "critic_m.", "critic_v.")):
                 assert not torch.equal(before[k], after[k]), (f.total_it, k)
     assert f.critic_step == 6 and f.actor1_step == 3 and f.actor2_step == 3
-
-
-def _f64(net):
-    return copy.deepcopy(net).double().requires_grad_(True)
 
 
 def test_fused_daddpg_gradients_equal_float64_autograd():

@@ -7,7 +7,7 @@ import json
 import pytest
 import torch
 
-import pop2_common as K
+import pop_common as K
 
 pytestmark = pytest.mark.gpu
 KIND = "daddpg"

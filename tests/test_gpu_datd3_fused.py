@@ -11,29 +11,19 @@ import numpy as np
 import pytest
 import torch
 
+import learner_gpu as G
 from datd3_golden import KEYS, NETS, expected_losses, load_train_fixture
-from test_gpu_td3_fused import _assert_grads
+from learner_gpu import DEV, assert_grads as _assert_grads, batch as _batch, f64_net as _f64, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ALGOS = ["datd3", "darc"]
 REACH_ITERATIONS = 140
 
 
-def _classes(algo):
+def _learners(algo):
     from armenv.datd3 import DARC, DATD3
     from armenv.fused_datd3 import FusedDARC, FusedDATD3
     return (DARC, FusedDARC) if algo == "darc" else (DATD3, FusedDATD3)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _batch(gen, B, D=6):
-    return dict(states=torch.rand(B, D, device=DEV, generator=gen), actions=torch.rand(B, 3, device=DEV, generator=gen) * 1.4 - 0.7,
-                next_states=torch.rand(B, D, device=DEV, generator=gen), rewards=torch.rand(B, device=DEV, generator=gen) - 0.5,
-                dones=(torch.rand(B, device=DEV, generator=gen) < 0.1).to(torch.uint8))
 
 
 def _noise(gen, B):
@@ -41,16 +31,7 @@ def _noise(gen, B):
 
 
 def _state(f):
-    """every tensor a fused update may write, by name"""
-    out = {}
-    for name in NETS:
-        for k, v in getattr(f, name).state_dict().items():
-            out[f"{name}.{k}"] = v.clone()
-    for name in NETS[:4]:
-        for mv in ("_m", "_v"):
-            for i, t in enumerate(getattr(f, name + mv)):
-                out[f"{name}{mv}.{i}"] = t.clone()
-    return out
+    return G.state(f, NETS, NETS[:4])
 
 
 def _steps(f):
@@ -62,7 +43,7 @@ def test_fused_update_reproduces_the_golden_updates(algo):
     """G17 / G18 on the fused path with the recorded noise through noise_dev: the reference's eight updates (B = 64) from
     torch.manual_seed(0)'s initial weights: losses 2e-5 relative, >= 99.9 % of each tensor's elements within 2e-5 and none beyond
     7e-3, forward values of all eight nets on batch 0 within 1e-4, the four optimisers' step counters 4 / 4 / 4 / 4."""
-    T, F = _classes(algo)
+    T, F = _learners(algo)
     darc = algo == "darc"
     g = load_train_fixture(algo + "_train_seed0")
     torch.manual_seed(0)
@@ -98,10 +79,6 @@ def test_fused_update_reproduces_the_golden_updates(algo):
             assert err < 1e-4, (name, err)
 
 
-def _f64(net):
-    return copy.deepcopy(net).double().requires_grad_(True)
-
-
 def _critic_loss64(before, f, batch, noise, k, darc, w):
     """float64 autograd restatement of the stepped critic's loss over the nets `before` the update"""
     s, a, s2 = (batch[x].double() for x in ("states", "actions", "next_states"))
@@ -124,7 +101,7 @@ def _grad_run(algo, w, ref_w):
     """Eight updates (k = 1, 2, 1, 2, ...) at B = 2048 with beta1 = 0, so the first moments after an update ARE the gradients it
     applied; the float64 reference uses regulariser weight `ref_w`.  Returns (number of updates whose every tensor is within the tight
     bound, number of updates).  _assert_grads raises when a tensor is beyond the loose bound."""
-    T, F = _classes(algo)
+    T, F = _learners(algo)
     darc = algo == "darc"
     kw = dict(regularization_weight=w) if darc else {}
     torch.manual_seed(0)
@@ -186,7 +163,7 @@ def test_darc_regulariser_is_exercised_by_the_gradient_check():
 def test_fused_update_owns_its_actor_and_critic_only(algo):
     """update(k) leaves everything of the other index bitwise unchanged -- the other actor, the other critic (DARC reads it), their
     moments and their targets -- and what it owns has moved; the step counters follow."""
-    _, F = _classes(algo)
+    _, F = _learners(algo)
     torch.manual_seed(4)
     f = F(6, 3, 0.7, device=DEV)
     gen = torch.Generator(device=DEV); gen.manual_seed(4)
@@ -252,7 +229,7 @@ def test_in_kernel_noise_is_keyed_by_seed_and_draw_and_shared_by_both_proposals(
 def test_fused_learner_follows_eager_torch_free_running(algo):
     """40 train calls (80 updates) of each learner at B = 2048 from the same start with shared noise: losses within 5e-3, the eight
     nets within 1e-2 on a held-out batch (test_fused_daddpg_follows_eager_torch_free_running's tolerances); the actors really moved."""
-    T, F = _classes(algo)
+    T, F = _learners(algo)
     torch.manual_seed(3)
     a = T(6, 3, 0.7, device=DEV)
     b = F(6, 3, 0.7, device=DEV)
@@ -285,7 +262,7 @@ def test_fused_update_shapes(B, D, algo):
     gradients against the torch learner's .grad as in _assert_grads.  Both learners keep beta1 = 0.9, so the fused gradient is
     recovered from the first moments: (m_new - beta1 m_old) / (1 - beta1).  Before update 2 the fused learner takes the torch
     learner's state again, so each update is compared from identical states."""
-    T, F = _classes(algo)
+    T, F = _learners(algo)
     torch.manual_seed(1)
     t = T(D, 3, 0.4, device=DEV)
     f = F(D, 3, 0.4, device=DEV)
@@ -310,7 +287,7 @@ def test_fused_update_shapes(B, D, algo):
 def test_fused_update_is_deterministic_across_runs_and_streams(algo):
     """Three learners from the same state, ten train calls on the same batches with the in-kernel noise, two on the default stream
     and one on a side stream: parameters, moments and losses are bitwise equal."""
-    _, F = _classes(algo)
+    _, F = _learners(algo)
     agents = []
     for _ in range(3):
         torch.manual_seed(2)
@@ -343,7 +320,7 @@ def test_fused_update_captured_in_a_graph_equals_direct_calls(algo):
     (step numbers 1 / 1, draw 1), so the direct calls repeat them."""
     import ctypes as C
     from armenv import _lib as L
-    _, F = _classes(algo)
+    _, F = _learners(algo)
     gen = torch.Generator(device=DEV); gen.manual_seed(6)
     batch = _batch(gen, 2048)
     noise = _noise(gen, 2048)
@@ -399,7 +376,7 @@ def test_training_loop_learns_reach_with_the_fused_learner(algo):
     """train_reach(algo, learner="fused"): the bar of the TD3 / DADDPG learning tests (>= 90 % success over the last log window of
     140 iterations, more than 5000 episodes); and train_push runs with finite parameters."""
     from armenv.train import train_push
-    _, F = _classes(algo)
+    _, F = _learners(algo)
     assert isinstance(_reach(algo, "fused"), F)
     agent, hist = train_push(num_envs=256, iterations=8, rollout_steps=16, updates=4, batch_size=256, window_steps=64, max_steps=20,
                              log_every=4, log=lambda s_: None, algo=algo, learner="fused")
@@ -410,5 +387,5 @@ def test_training_loop_learns_reach_with_the_fused_learner(algo):
 @pytest.mark.parametrize("algo", ALGOS)
 def test_training_loop_learns_reach_with_the_graphed_torch_learner(algo):
     """train_reach(algo, learner="torch") with the update replayed from hipGraphs (two replays per train_graphed): the same bar."""
-    T, _ = _classes(algo)
+    T, _ = _learners(algo)
     assert isinstance(_reach(algo, "torch"), T)

@@ -5,7 +5,7 @@ depend on the grid, so member p of a population update equals armenv_datd3_updat
 import pytest
 import torch
 
-import pop2_common as K
+import pop_common as K
 
 pytestmark = pytest.mark.gpu
 KINDS = ("datd3", "darc")

@@ -8,29 +8,16 @@ import random
 import pytest
 import torch
 
-import pop2_common as pc
+import pop_common as pc
 
 pytestmark = pytest.mark.gpu
 DEV = pc.DEV
 KINDS = ("td3", "daddpg", "datd3", "darc")
-MID_RUN = dict(pc.MID_RUN, td3=dict(total_it=4, critic_step=4, actor_step=1))
-
-
-def _classes(kind):
-    if kind == "td3":
-        from armenv.fused_td3 import FusedTD3
-        from armenv.fused_td3_pop import FusedTD3Population
-        return FusedTD3Population, FusedTD3, "td3"
-    return pc.classes(kind)
 
 
 def _population(kind, P, gen_seed, D=6, **values):
     """a population whose members all differ in every tensor (moments included), counters set mid-run"""
-    pop = _classes(kind)[0](P, D, 3, 0.7, device=DEV, seed=11, **values)
-    pc.randomise(pop, pc.generator(gen_seed))
-    for name, value in MID_RUN[kind].items():
-        setattr(pop, name, value)
-    return pop
+    return pc.population(kind, P, D, pc.generator(gen_seed), **values)
 
 
 def _tensors(pop):
@@ -128,10 +115,6 @@ def test_a_refused_plan_raises_and_leaves_every_tensor_unchanged():
     assert _equal(_tensors(pop), before) and [pop.hyper(p) for p in range(3)] == rows
 
 
-def _train(kind, pop, b, noise):
-    return [pop.train(b, noise=noise)] if kind == "td3" else pc.train(kind, pop, b, noise)
-
-
 @pytest.mark.parametrize("kind", ["daddpg", "td3"])
 def test_an_exploited_member_trains_like_its_source(kind):
     """After exploit([0, 0, 2]) members 0 and 1 are given the same batch (TD3: and the same target-policy noise): every `train` leaves
@@ -149,8 +132,8 @@ def test_an_exploited_member_trains_like_its_source(kind):
         if kind == "td3":
             noise = pc.noise_for(gen, P, B)
             noise[1].copy_(noise[0])
-        losses = _train(kind, pop, b, noise)
-        twin_losses = _train(kind, twin, b, noise)
+        losses = pc.train(kind, pop, b, noise)
+        twin_losses = pc.train(kind, twin, b, noise)
         torch.cuda.synchronize(DEV)
         assert _equal(pc.state(pop, 0), pc.state(pop, 1)), it
         assert all(torch.equal(x[0], x[1]) for x in losses), it
@@ -160,7 +143,7 @@ def test_an_exploited_member_trains_like_its_source(kind):
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_exploit_copies_the_hyper_parameters_only_when_asked(kind):
-    stem = _classes(kind)[2]
+    stem = pc.classes(kind)[2]
     values = dict(tau=[0.005, 0.01, 0.02], critic_lr=[1e-3, 2e-3, 3e-3])
     pop = _population(kind, 3, 10, **values)
     rows = [pop.hyper(p) for p in range(3)]

@@ -10,12 +10,11 @@ import numpy as np
 import pytest
 import torch
 
-import pop2_common as pc
+import pop_common as pc
 
 pytestmark = pytest.mark.gpu
 DEV = pc.DEV
 KINDS = ("td3", "daddpg", "datd3", "darc")
-MID_RUN = dict(pc.MID_RUN, td3=dict(total_it=4, critic_step=4, actor_step=1))
 # (low, high) of the random draws; gamma, tau and q_weight live in [0, 1], the others are >= 0
 RANGES = dict(actor_lr=(1e-4, 3e-3), critic_lr=(1e-4, 3e-3), tau=(1e-3, 5e-2), gamma=(0.9, 0.999), policy_noise=(0.05, 0.4),
               noise_clip=(0.2, 0.8), q_weight=(0.1, 0.9), regularization_weight=(1e-3, 5e-2))
@@ -24,17 +23,9 @@ EDGES = (dict(gamma=0.0, tau=1.0, q_weight=0.0), dict(gamma=1.0, tau=0.0, policy
          dict(critic_lr=0.0, regularization_weight=0.0), dict())
 
 
-def _classes(kind):
-    if kind == "td3":
-        from armenv.fused_td3 import FusedTD3
-        from armenv.fused_td3_pop import FusedTD3Population
-        return FusedTD3Population, FusedTD3, "td3"
-    return pc.classes(kind)
-
-
 def _member_values(kind, P, rng, rotate=0, edges=True):
     """{name: [P values]}: distinct per member and per field, member p holding the edge values of EDGES[(p + rotate) % 5]"""
-    names = _classes(kind)[0].sweepable()
+    names = pc.classes(kind)[0].sweepable()
     values = {n: [float(np.float32(rng.uniform(*RANGES[n]))) for _ in range(P)] for n in names}
     for p in range(P if edges else 0):
         for n, v in EDGES[(p + rotate) % len(EDGES)].items():
@@ -45,27 +36,14 @@ def _member_values(kind, P, rng, rotate=0, edges=True):
 
 def _population(kind, P, D, gen, values, seed=11, force=True):
     """a population with random state, counters set mid-run and the members' `values`, on the per-member entry point"""
-    pop = _classes(kind)[0](P, D, 3, 0.7, device=DEV, seed=seed, **values)
+    pop = pc.population(kind, P, D, gen, seed=seed, **values)
     pop.always_hyper = force
-    if gen is not None:
-        pc.randomise(pop, gen)
-    for name, value in MID_RUN[kind].items():
-        setattr(pop, name, value)
     assert pop.entry_point.endswith("_pop_update_hyper") or not force
     return pop
 
 
-def _train(kind, learner, b, noise=None):
-    """one `train`; the losses as a list of tensors"""
-    if kind == "td3":
-        return [learner.train(b, noise=noise)]
-    return pc.train(kind, learner, b, noise)
-
-
 def _noise(kind, gen, P, B, given):
-    if kind == "daddpg" or not given:
-        return None
-    return pc.noise_for(gen, P, B) if kind == "td3" else (pc.noise_for(gen, P, B), pc.noise_for(gen, P, B))
+    return pc.train_noises(kind, gen, P, B, 1)[0] if given else None
 
 
 def _member_noise(noise, p):
@@ -101,13 +79,13 @@ def test_every_member_equals_the_single_update_with_its_own_values_bit_for_bit(k
     singles = [pop.export_member(p) for p in range(P)]
     for p, single in enumerate(singles):
         assert all(getattr(single, n) == values[n][p] for n in values), p
-        assert single.total_it == MID_RUN[kind]["total_it"] and (kind == "daddpg" or single.seed == 11 + p)
+        assert single.total_it == pc.MID_RUN[kind]["total_it"] and (kind == "daddpg" or single.seed == 11 + p)
     for it, given in enumerate(TRAINS[kind]):
         b = pc.batch(gen, P, B, D)
         noise = _noise(kind, gen, P, B, given)
-        losses = _train(kind, pop, b, noise)
+        losses = pc.train(kind, pop, b, noise)
         for p, single in enumerate(singles):
-            ls = _train(kind, single, pc.member_batch(b, p), _member_noise(noise, p))
+            ls = pc.train(kind, single, pc.member_batch(b, p), _member_noise(noise, p))
             assert all(torch.equal(x, y[p]) for x, y in zip(ls, losses)), (it, p)
             bad = [k for k, (x, y) in enumerate(zip(pc.state(pop, p), pop._single_state(single))) if not torch.equal(x, y)]
             assert not bad, (it, p, bad)
@@ -121,7 +99,7 @@ def test_every_member_equals_the_single_update_with_its_own_values_bit_for_bit(k
 
 def _run(kind, P, B, D, batches, noises, values, force=True, seed_gen=3):
     pop = _population(kind, P, D, pc.generator(seed_gen), values, force=force)
-    losses = [torch.stack(_train(kind, pop, b, n)) for b, n in zip(batches, noises)]
+    losses = [torch.stack(pc.train(kind, pop, b, n)) for b, n in zip(batches, noises)]
     return pop, torch.stack(losses)
 
 
@@ -156,7 +134,7 @@ def _prepared(kind, pop, B, b, noise, updates, ws=None, loss=None):
     it is NOW) once per entry of `updates` -- TD3: with_actor values; the others: update_actor values -- with fixed step numbers, on
     the current stream"""
     from armenv import _lib as L
-    stem = _classes(kind)[2]
+    stem = pc.classes(kind)[2]
     P, D = pop.members, pop.state_dim
     pop._bind(pop._static_args())
     pa, table, fn = pop._args, pop._table, pop._bound_fn
@@ -174,19 +152,9 @@ def _prepared(kind, pop, B, b, noise, updates, ws=None, loss=None):
     def call():
         for i, k in enumerate(updates):
             one.loss_dev = loss[i].data_ptr()
-            if kind == "td3":
-                one.with_actor = k
-            else:
-                one.update_actor = k
-            if kind != "daddpg":
-                one.draw = 7 + i
-                one.noise_dev = noise[i].data_ptr() if noise is not None else None
+            pc.set_update(one, kind, k, 7 + i, None if noise is None else noise[i])
             L.check(fn(C.byref(pa), table, C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)))
     return call, loss, (ws, pa, table)
-
-
-def _updates(kind):
-    return (0, 1) if kind == "td3" else (1, 2)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -208,13 +176,13 @@ def test_nothing_is_written_outside_the_stacks_and_the_workspace(kind):
 
     for name in list(pop.stacks):
         pop.stacks[name] = [padded(t) for t in pop.stacks[name]]
-    ws_bytes = getattr(L.load(), "armenv_%s_pop_workspace_bytes" % _classes(kind)[2])(D, 256, B, P)
+    ws_bytes = getattr(L.load(), "armenv_%s_pop_workspace_bytes" % pc.classes(kind)[2])(D, 256, B, P)
     ws = padded(torch.zeros(ws_bytes // 4, device=DEV)).view(torch.uint8)
     assert ws.numel() == ws_bytes and ws.data_ptr() % 16 == 0
     loss = padded(torch.zeros(2, P, device=DEV))
     held = {k: padded(t) for k, t in pc.batch(gen, P, B, D).items()}
     before = [t.clone() for t in pc.state(pop, 1)]
-    call, _, _keep = _prepared(kind, pop, B, held, None, _updates(kind), ws=ws, loss=loss)
+    call, _, _keep = _prepared(kind, pop, B, held, None, pc.updates(kind), ws=ws, loss=loss)
     call()
     torch.cuda.synchronize(DEV)
     for buf in bufs:
@@ -236,7 +204,7 @@ def test_a_member_with_zero_rates_stands_still_while_its_neighbours_move(kind):
     n_nets = 6 * len(pop._NETS)
     before = [[t.clone() for t in pc.state(pop, p)] for p in range(P)]
     for _ in range(3 if kind in ("td3", "daddpg") else 2):         # TD3: total_it 5, 6, 7 -- the actor and the targets move at 6
-        losses = _train(kind, pop, pc.batch(gen, P, B, D))
+        losses = pc.train(kind, pop, pc.batch(gen, P, B, D))
     assert all(bool(torch.isfinite(x).all()) for x in losses)
     assert _equal(before[1][:n_nets], pc.state(pop, 1)[:n_nets])
     assert not _equal(before[1][n_nets:], pc.state(pop, 1)[n_nets:])
@@ -258,10 +226,10 @@ def test_the_update_is_deterministic_across_runs_and_streams(kind):
     losses = [[], [], []]
     for b in batches:
         for k in (0, 1):
-            losses[k] += _train(kind, pops[k], b)
+            losses[k] += pc.train(kind, pops[k], b)
         side.wait_stream(torch.cuda.current_stream(DEV))
         with torch.cuda.stream(side):
-            losses[2] += _train(kind, pops[2], b)
+            losses[2] += pc.train(kind, pops[2], b)
         torch.cuda.current_stream(DEV).wait_stream(side)
     torch.cuda.synchronize(DEV)
     for k in (1, 2):
@@ -277,7 +245,7 @@ def test_a_captured_update_keeps_the_values_of_capture_time(kind):
     P, B, D = 3, 257, 6
     gen = pc.generator(61)
     b = pc.batch(gen, P, B, D)
-    updates = _updates(kind)
+    updates = pc.updates(kind)
     noise = None if kind == "daddpg" else [pc.noise_for(gen, P, B) for _ in updates]
     values = _member_values(kind, P, np.random.default_rng(61), edges=False)
     direct, graphed, fresh = (_population(kind, P, D, pc.generator(62), values) for _ in range(3))

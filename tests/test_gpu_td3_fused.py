@@ -8,19 +8,9 @@ import pytest
 import torch
 
 from conftest import golden_npz
+from learner_gpu import DEV, assert_grads as _assert_grads, batch as _batch, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _batch(gen, B, D=6):
-    return dict(states=torch.rand(B, D, device=DEV, generator=gen), actions=torch.rand(B, 3, device=DEV, generator=gen) * 1.4 - 0.7,
-                next_states=torch.rand(B, D, device=DEV, generator=gen), rewards=torch.rand(B, device=DEV, generator=gen) - 0.5,
-                dones=(torch.rand(B, device=DEV, generator=gen) < 0.1).to(torch.uint8))
 
 
 def test_fused_td3_reproduces_the_golden_updates():
@@ -77,27 +67,11 @@ def _one_update_from_identical_state(t, f, batch, noise, monkeypatch):
     return lt, lf, with_actor, pairs
 
 
-def _assert_grads(pairs, where):
-    """Every tensor within 5e-2 of its own norm (Frobenius) and of its largest |g|; returns whether every tensor is also within 1e-4
-    of its largest |g| (+ 1e-7) element by element -- the rule.  The exceptions are relu boundaries: a pre-activation within rounding
-    of zero is active in one learner and not in the other.  In the critic's second layer that moves one row's delta: one row of the
-    fc2 weight gradient and, through W2, a rank-one difference over the whole fc1 weight gradient (measured on update 20 of the 40
-    below: fc2 weight 1.1e-5 against a largest |g| of 4.3e-4, fc1 weight 8.2e-7 against 2.8e-4; every tensor of the 20 updates before it
-    within 1e-4)."""
-    tight = True
-    for k, (gt, gf) in enumerate(pairs):
-        gmax, d = float(gt.abs().max()), gt - gf
-        err, rel = float(d.abs().max()), float(d.norm() / max(float(gt.norm()), 1e-30))
-        assert err <= 5e-2 * gmax + 1e-7 and rel <= 5e-2, (where, k, tuple(gt.shape), err, gmax, rel)
-        tight = tight and err <= 1e-4 * gmax + 1e-7
-    return tight
-
-
 def test_fused_gradients_equal_torch_from_identical_state(monkeypatch):
     """40 consecutive updates at B = 2048 (13 of them with the actor step): before each, the fused learner takes the torch learner's
     parameters, moments and step counters; both see the same batch and noise.  The gradient the fused update applied equals the
     torch learner's .grad per tensor to 1e-4 of that tensor's largest element on at least 36 of the 40 updates, and within 5e-2 on all
-    (relu boundaries, _assert_grads), and the losses agree to 1e-5 relative.  Gradients, not parameters: Adam's normalisation
+    (relu boundaries, learner_gpu.assert_grads), and the losses agree to 1e-5 relative.  Gradients, not parameters: Adam's normalisation
     turns last-bit gradient differences into lr-sized parameter differences."""
     from armenv.fused_td3 import FusedTD3
     from armenv.td3 import TD3

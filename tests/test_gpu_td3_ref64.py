@@ -6,7 +6,6 @@ The gradient the kernel applied is read exactly: with betas = (0, 0.999), Adam's
 Each stage is compared on its own (teacher forcing): the actor's gradient through the kernel's own stepped critic, the Adam steps
 fed the kernel's own gradient.  C is one constant per kind of quantity, calibrated on the MI355X (profiles/td3_fused_ref64_errors.txt
 records the largest measured ratios; each C is at most 8x the largest)."""
-import json
 import os
 
 import numpy as np
@@ -14,26 +13,24 @@ import pytest
 import torch
 
 import td3_ref64 as R
+from learner_gpu import DEV, Bounds, f64 as _f64
 
 pytestmark = pytest.mark.gpu
 NOISE_C = 0.015
-DEV = "cuda:0"
 U = R.U
 C = dict(critic_grad=1.0, actor_grad=0.5, loss=0.05, adam=16.0, noise=NOISE_C)
 AMB_MAX = 1e-3                   # at most this fraction of relu units may be ambiguous, or the allowance would make the test vacuous
 NO_ACTOR = 1 << 40               # a policy_freq under which no update takes the actor step
-RATIOS = {}                      # (kind, case) -> largest |got - ref| - allowance, in units of 2^-24 M
+BOUNDS = Bounds(C, AMB_MAX)
+_check, _grad_failures, _adam_failures = BOUNDS.check, BOUNDS.grad_failures, BOUNDS.adam_failures
+_ambiguity_is_rare = BOUNDS.ambiguity_is_rare
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _ratio_log():
     """ARMENV_TD3_REF64_RATIOS=<path>: write the largest measured ratio per kind and case there (calibration of C)"""
     yield
-    path = os.environ.get("ARMENV_TD3_REF64_RATIOS")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as fh:
-            json.dump({"%s|%s" % k: v for k, v in sorted(RATIOS.items())}, fh, indent=1)
+    BOUNDS.write(os.environ.get("ARMENV_TD3_REF64_RATIOS"))
 
 
 def _f32(x):
@@ -95,10 +92,6 @@ def _state(f):
                         f.actor_step, f.critic_step, device=DEV)
 
 
-def _f64(xs):
-    return [t.detach().to(torch.float64) for t in (xs.parameters() if hasattr(xs, "parameters") else xs)]
-
-
 def _kernel_update(f, batch, noise):
     """one fused update; returns (state before, with_actor, loss, the kernel's outputs in float64)"""
     st = _state(f)
@@ -108,48 +101,6 @@ def _kernel_update(f, batch, noise):
                target_critic=_f64(f.target_critic), actor=_f64(f.actor), actor_m=_f64(f.actor_m), actor_v=_f64(f.actor_v),
                target_actor=_f64(f.target_actor))
     return st, with_actor, loss, got
-
-
-def _check(kind, case, got, ref, mag, allow=None, record=True):
-    """number of elements beyond C[kind] 2^-24 mag + allow; `record`: keep the largest ratio for the calibration log"""
-    n, ratio = R.bad_elements(got, ref, mag, torch.zeros_like(mag) if allow is None else allow, C[kind])
-    if record:
-        RATIOS[(kind, case)] = max(RATIOS.get((kind, case), 0.0), ratio)
-    return n
-
-
-def _grad_failures(case, got, out, with_actor, record=True):
-    """quantities whose kernel gradient / loss lies beyond the bound around the reference `out` (beta1 = 0: m is the gradient)"""
-    bad = []
-    chk = lambda *a: _check(*a, record=record)
-    lt = torch.tensor([got["loss"]], dtype=torch.float64)
-    if chk("loss", case, lt, torch.tensor([out["loss"]], dtype=torch.float64), torch.tensor([out["loss_mag"]], dtype=torch.float64)):
-        bad.append("loss")
-    for side in ("critic",) + (("actor",) if with_actor else ()):
-        for k, g in enumerate(got[side + "_m"]):
-            if chk(side + "_grad", case, g, out[side + "_grad"][k], out[side + "_grad_mag"][k], out[side + "_grad_allow"][k]):
-                bad.append("%s_grad%d" % (side, k))
-    return bad
-
-
-def _adam_failures(case, got, out, with_actor, sides=("critic", "actor"), record=True):
-    """Adam-stepped parameters, moments and soft-updated targets beyond C_adam 2^-24 of their magnitudes"""
-    bad = []
-    chk = lambda *a: _check(*a, record=record)
-    for side in sides:
-        if side == "actor" and not with_actor:
-            continue
-        names = [side, side + "_m", side + "_v"] + (["target_" + side] if with_actor else [])
-        for name in names:
-            for k, t in enumerate(got[name]):
-                if chk("adam", case, t, out[name][k], out[name + "_mag"][k]):
-                    bad.append("%s%d" % (name, k))
-    return bad
-
-
-def _ambiguity_is_rare(out):
-    assert out["ambiguous"] <= AMB_MAX * out["units"], (out["ambiguous"], out["units"])
-    RATIOS[("ambiguous_fraction", "max")] = max(RATIOS.get(("ambiguous_fraction", "max"), 0.0), out["ambiguous"] / out["units"])
 
 
 GRAD_SHAPES = [(B, 6) for B in (1, 2, 3, 63, 64, 65, 255, 256, 257, 511, 1000, 2048, 4097, 65536)] + \

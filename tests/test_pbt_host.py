@@ -8,16 +8,12 @@ import os
 import random
 import subprocess
 import sys
-import tempfile
 
 import pytest
 
 from conftest import ROOT
+from learner_host import ctypes_layout, header_layout, learner_kernels, refused  # noqa: F401
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
-import isa  # noqa: E402
-
-HEADER_DIR = os.path.join(ROOT, "include")
 FIELDS = ("device", "members", "tensors", "reserved", "src", "base", "elems")
 TD3_ROW = dict(actor_lr=1e-3, critic_lr=1e-3, tau=0.005, gamma=0.98, policy_noise=0.2, noise_clip=0.5, expl_sigma=0.686)
 TD3_NAMES = ("actor_lr", "critic_lr", "tau", "policy_noise", "noise_clip", "expl_sigma")      # sweepable minus gamma, plus expl_sigma
@@ -27,19 +23,11 @@ def test_struct_layout_matches_the_header_the_symbol_resolves_and_the_abi_versio
     from armenv import _lib as L
     A = L.ArmEnvPopExploitArgs
     assert tuple(n for n, _ in A._fields_) == FIELDS
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "armenv.h"', "int main(void) {",
-             '  printf("%zu %d\\n", sizeof(ArmEnvPopExploitArgs), ARMENV_EXPLOIT_MAX_TENSORS);']
-    lines += ['  printf("%%zu\\n", offsetof(ArmEnvPopExploitArgs, %s));' % n for n in FIELDS]
-    lines += ["  _Static_assert(__builtin_types_compatible_p(__typeof__(&armenv_pop_exploit), "
-              "int (*)(const ArmEnvPopExploitArgs *, void *)), \"armenv_pop_exploit\");", "  return 0;", "}"]
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        with open(src, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
-        subprocess.run(["gcc", "-std=gnu11", "-Wall", "-Werror", "-I", HEADER_DIR, "-o", exe, src], check=True)
-        out = [int(x) for x in subprocess.run([exe], check=True, stdout=subprocess.PIPE, text=True).stdout.split()]
-    assert out[0] == C.sizeof(A) == 40 and out[1] == L.EXPLOIT_MAX_TENSORS == 128
-    assert out[2:] == [getattr(A, n).offset for n in FIELDS]
+    checks = ["_Static_assert(__builtin_types_compatible_p(__typeof__(&armenv_pop_exploit), "
+              "int (*)(const ArmEnvPopExploitArgs *, void *)), \"armenv_pop_exploit\");"]
+    sizes, offsets = header_layout(A, extra=("ARMENV_EXPLOIT_MAX_TENSORS",), checks=checks, std="gnu11", werror=True)
+    assert sizes[0] == C.sizeof(A) == 40 and sizes[1] == L.EXPLOIT_MAX_TENSORS == 128
+    assert [n for n, _ in ctypes_layout(A)] == list(FIELDS) and offsets == [getattr(A, n).offset for n in FIELDS]
     lib = L.load()
     assert lib.armenv_pop_exploit is not None
     assert L.SYMBOLS["armenv_pop_exploit"] == (C.c_int, [C.POINTER(A), C.c_void_p])
@@ -66,10 +54,7 @@ def _call(a):
 
 
 def _refused(a):
-    rc, msg = _call(a)
-    assert rc == -1, (rc, msg)                       # ARMENV_EINVAL, not ENODEV: nothing touched the device
-    assert msg.startswith("armenv_pop_exploit"), msg
-    return msg
+    return refused("armenv_pop_exploit", C.byref(a) if a is not None else None, None)
 
 
 def test_null_arguments_are_refused():
@@ -131,18 +116,8 @@ def test_an_identity_plan_returns_ok_without_a_device():
         assert rc == 0, (rc, msg)
 
 
-@pytest.fixture(scope="module")
-def learner_kernels():
-    if not os.path.exists(isa.LIB):
-        pytest.skip("libarmenv.so is not built")
-    if not os.path.exists(os.path.join(isa.LLVM, "llvm-objdump")):
-        pytest.skip("the ROCm LLVM tools (llvm-objdump, llvm-readelf) are not installed")
-    rows = [r for r in isa.all_kernels() if "armenv::learner::" in r[1]]
-    return {dm.split("armenv::learner::")[1].split("(")[0]: (md, ins) for _, dm, md, ins in rows}
-
-
 def test_the_exploit_kernel_is_in_the_code_object_without_scratch_lds_or_spills(learner_kernels):
-    """test_td3_fused_host.py holds every armenv::learner:: kernel, this one included, to no scratch, no spills and no atomics; here:
+    """test_td3_fused_host.py holds all of learner_host.learner_kernels, this one included, to no scratch, no spills and no atomics; here:
     it is there, uses no LDS, and copies 16 bytes wide."""
     assert "pop_exploit_kernel" in learner_kernels, sorted(learner_kernels)
     md, ins = learner_kernels["pop_exploit_kernel"]

@@ -3,66 +3,26 @@ include/armenv.h): the ctypes structs agree with the header, the workspace queri
 validated before any HIP call, the population classes' stacks hold what P seeded single learners hold, and the four population head
 kernels are in the built code object."""
 import ctypes as C
-import os
-import subprocess
-import sys
-import tempfile
 
 import pytest
 import torch
 
-from conftest import ROOT
+from learner_host import (AGENTS, POP_REFUSALS, POP_REFUSALS_DATD3, classes, ctypes_layout, fake_pop_args, header_layout,  # noqa: F401
+                          learner_kernels, refused)
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
-import isa  # noqa: E402
-
-HEADER_DIR = os.path.join(ROOT, "include")
 POP_KERNELS = ("daddpg_actor_head_pop_kernel", "daddpg_critic_head_pop_kernel", "datd3_actor_head_pop_kernel",
                "datd3_critic_head_pop_kernel")
-DADDPG_NETS = ("actor1", "actor2", "critic", "target_actor1", "target_actor2", "target_critic",
-               "actor1_m", "actor1_v", "actor2_m", "actor2_v", "critic_m", "critic_v")
-DATD3_NETS = ("actor1", "actor2", "critic1", "critic2", "target_actor1", "target_actor2", "target_critic1", "target_critic2",
-              "actor1_m", "actor1_v", "actor2_m", "actor2_v", "critic1_m", "critic1_v", "critic2_m", "critic2_v")
 ALGOS = ("daddpg", "datd3")
-
-
-def _c(algo):
-    """(pop struct, single struct, their C names, the stacks of `one`) of an entry point"""
-    from armenv import _lib as L
-    if algo == "daddpg":
-        return L.ArmEnvDaddpgPopArgs, L.ArmEnvDaddpgArgs, "ArmEnvDaddpgPopArgs", "ArmEnvDaddpgArgs", DADDPG_NETS
-    return L.ArmEnvDatd3PopArgs, L.ArmEnvDatd3Args, "ArmEnvDatd3PopArgs", "ArmEnvDatd3Args", DATD3_NETS
-
-
-def _ctypes_layout(struct, prefix=""):
-    """[(C member path, offset)] of every scalar member of a ctypes struct, nested structs flattened"""
-    out = []
-    for name, typ in struct._fields_:
-        off = getattr(struct, name).offset
-        if isinstance(typ, type) and issubclass(typ, C.Structure):
-            out += [(f"{prefix}{name}.{k}", off + o) for k, o in _ctypes_layout(typ, "")]
-        else:
-            out.append((prefix + name, off))
-    return out
 
 
 @pytest.mark.parametrize("algo", ALGOS)
 def test_struct_layout_matches_the_header(algo):
-    Pop, One, pop_name, one_name, nets = _c(algo)
-    members = _ctypes_layout(Pop)
+    Pop, One, nets = (AGENTS[algo][k] for k in ("pop_args", "args", "nets"))
+    members = ctypes_layout(Pop)
     assert ("members", Pop.members.offset) in members and any(m.startswith("one.%s." % nets[-1]) for m, _ in members)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "armenv.h"', "int main(void) {",
-             '  printf("%%zu %%zu\\n", sizeof(%s), sizeof(%s));' % (pop_name, one_name)]
-    lines += ['  printf("%%zu\\n", offsetof(%s, %s));' % (pop_name, m) for m, _ in members]
-    lines += ["  return 0;", "}"]
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        with open(src, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
-        subprocess.run(["gcc", "-std=c99", "-Wall", "-I", HEADER_DIR, "-o", exe, src], check=True)
-        out = subprocess.run([exe], check=True, stdout=subprocess.PIPE, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(Pop) and int(out[1]) == C.sizeof(One)
-    assert [int(x) for x in out[2:]] == [o for _, o in members], members
+    sizes, offsets = header_layout(Pop, extra=("sizeof(%s)" % One.__name__,))
+    assert sizes == [C.sizeof(Pop), C.sizeof(One)]
+    assert offsets == [o for _, o in members], members
     assert Pop.members.offset == C.sizeof(One)
 
 
@@ -94,86 +54,21 @@ def test_population_workspace_refuses_unsupported_sizes(algo):
     assert pop(6, 256, 0, 2) == -1 and pop(6, 256, (1 << 20) + 1, 2) == -1
 
 
-def _args(algo, P=3, B=64, D=6, darc=0):
-    """Arguments that pass every check but the one a test breaks: fake (never dereferenced) 16-byte aligned device pointers.
-    NOT to be passed unmodified -- a valid set would be enqueued."""
-    from armenv import _lib as L
-    Pop, _, _, _, nets = _c(algo)
-    pa = Pop()
-    pa.members = P
-    a = pa.one
-    a.device, a.state_dim, a.action_dim, a.hidden_dim, a.batch = 0, D, 3, 256, B
-    a.action_bound, a.gamma, a.tau = 0.7, 0.98, 0.005
-    a.actor_lr, a.critic_lr, a.beta1, a.beta2, a.eps = 1e-3, 1e-3, 0.9, 0.999, 1e-8
-    a.critic_step, a.actor_step, a.update_actor = 1, 1, 1
-    if algo == "datd3":
-        a.policy_noise, a.noise_clip, a.darc, a.q_weight, a.regularization_weight = 0.2, 0.5, darc, 0.2, 0.005
-    addr = [0x10000000]
-
-    def ptr():
-        addr[0] += 0x1000000
-        return addr[0]
-    for net in nets:
-        m = getattr(a, net)
-        for k in ("W1", "b1", "W2", "b2", "W3", "b3"):
-            setattr(m, k, ptr())
-    for k in ("states_dev", "actions_dev", "next_states_dev", "rewards_dev", "dones_dev", "workspace_dev"):
-        setattr(a, k, ptr())
-    a.workspace_bytes = getattr(L.load(), "armenv_%s_pop_workspace_bytes" % algo)(D, 256, B, P)
-    assert a.workspace_bytes > 0
-    return pa
-
-
-def _one(field, value):
-    return lambda pa: setattr(pa.one, field, value)
-
-
 def _refused(algo, pa):
-    from armenv import _lib as L
-    lib = L.load()
-    fn = "armenv_%s_pop_update" % algo
-    rc, msg = getattr(lib, fn)(C.byref(pa) if pa is not None else None, None), lib.armenv_last_error().decode()
-    assert rc == -1, (rc, msg)                       # ARMENV_EINVAL, not ENODEV: nothing touched the device
-    assert msg.startswith(fn), msg
-    return msg
-
-
-COMMON = [
-    ("members", lambda pa: setattr(pa, "members", 0)),
-    ("members", lambda pa: setattr(pa, "members", 65)),
-    ("members", lambda pa: setattr(pa, "members", -1)),
-    ("update_actor", _one("update_actor", 0)),
-    ("update_actor", _one("update_actor", 3)),
-    ("target_actor2", lambda pa: setattr(pa.one.target_actor2, "W2", None)),
-    ("actor2_v", lambda pa: setattr(pa.one.actor2_v, "b3", pa.one.actor2_v.b3 + 4)),
-    ("states_dev", _one("states_dev", None)),
-    ("workspace_bytes", lambda pa: setattr(pa.one, "workspace_bytes", pa.one.workspace_bytes - 1)),
-    ("gamma", _one("gamma", float("nan"))),
-    ("batch", _one("batch", 0)),
-    ("hidden_dim", _one("hidden_dim", 128)),
-    ("actor_step", _one("actor_step", 0)),
-]
+    return refused("armenv_%s_pop_update" % algo, C.byref(pa) if pa is not None else None, None)
 
 
 @pytest.mark.parametrize("algo", ALGOS)
-@pytest.mark.parametrize("field,mutate", COMMON)
+@pytest.mark.parametrize("field,mutate", POP_REFUSALS["daddpg"])          # one table under both keys
 def test_bad_arguments_are_refused_before_any_device_call(algo, field, mutate):
-    pa = _args(algo)
+    pa = fake_pop_args(algo)
     mutate(pa)
     assert field in _refused(algo, pa)
 
 
-@pytest.mark.parametrize("field,darc,mutate", [
-    ("darc", 0, _one("darc", 2)),
-    ("darc", 0, _one("darc", -1)),
-    ("q_weight", 1, _one("q_weight", 1.5)),
-    ("q_weight", 1, _one("q_weight", -0.1)),
-    ("regularization_weight", 1, _one("regularization_weight", -1.0)),
-    ("policy_noise", 0, _one("policy_noise", -0.1)),
-    ("critic2_m", 1, lambda pa: setattr(pa.one.critic2_m, "W1", None)),
-])
+@pytest.mark.parametrize("field,darc,mutate", POP_REFUSALS_DATD3)
 def test_bad_datd3_arguments_are_refused_before_any_device_call(field, darc, mutate):
-    pa = _args("datd3", darc=darc)
+    pa = fake_pop_args("datd3", darc=darc)
     mutate(pa)
     assert field in _refused("datd3", pa)
 
@@ -181,7 +76,7 @@ def test_bad_datd3_arguments_are_refused_before_any_device_call(field, darc, mut
 @pytest.mark.parametrize("algo", ALGOS)
 def test_a_single_workspace_is_too_small_for_a_population(algo):
     from armenv import _lib as L
-    pa = _args(algo, P=2)
+    pa = fake_pop_args(algo, P=2)
     pa.one.workspace_bytes = getattr(L.load(), "armenv_%s_workspace_bytes" % algo)(6, 256, 64)
     msg = _refused(algo, pa)
     assert "workspace_bytes" in msg and "armenv_%s_pop_workspace_bytes" % algo in msg, msg
@@ -192,21 +87,13 @@ def test_null_args_are_refused(algo):
     assert "args" in _refused(algo, None)
 
 
-def _classes(kind):
-    from armenv.fused_daddpg import FusedDADDPG
-    from armenv.fused_daddpg_pop import FusedDADDPGPopulation
-    from armenv.fused_datd3 import FusedDARC, FusedDATD3
-    from armenv.fused_datd3_pop import FusedDARCPopulation, FusedDATD3Population
-    return dict(daddpg=(FusedDADDPGPopulation, FusedDADDPG, DADDPG_NETS), datd3=(FusedDATD3Population, FusedDATD3, DATD3_NETS),
-                darc=(FusedDARCPopulation, FusedDARC, DATD3_NETS))[kind]
-
-
 KINDS = ("daddpg", "datd3", "darc")
 
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_population_members_start_as_seeded_single_learners(kind):
-    Pop, Single, nets = _classes(kind)
+    Pop, Single, _ = classes(kind)
+    nets = AGENTS[kind]["nets"]
     torch.manual_seed(99)
     before = torch.get_rng_state()
     pop = Pop(3, 6, 3, 0.7, device="cpu", seed=5)
@@ -240,7 +127,7 @@ def test_population_members_start_as_seeded_single_learners(kind):
 
 @pytest.mark.parametrize("kind", KINDS)
 def test_member_parameters_are_views_into_the_stacks(kind):
-    Pop, _, _ = _classes(kind)
+    Pop, _, _ = classes(kind)
     pop = Pop(3, 6, 3, 0.7, device="cpu", seed=5)
     critic = "critic" if kind == "daddpg" else "critic2"
     W1 = pop.stacks["actor2"][0]
@@ -259,7 +146,7 @@ def test_member_parameters_are_views_into_the_stacks(kind):
 @pytest.mark.parametrize("kind", KINDS)
 def test_member_buffers_are_what_the_sampler_accepts(kind):
     """TrajectoryStore.sample(out=...) wants, per key, a contiguous tensor of the batch's shape and dtype on the store's device."""
-    Pop, _, _ = _classes(kind)
+    Pop, _, _ = classes(kind)
     pop = Pop(3, 9, 3, 0.4, device="cpu")
     with pytest.raises(RuntimeError):
         pop.member_buffers(0)
@@ -280,7 +167,7 @@ def test_member_buffers_are_what_the_sampler_accepts(kind):
 @pytest.mark.parametrize("kw", [dict(state_dim=13), dict(state_dim=0), dict(action_dim=2), dict(hidden_dim=128), dict(members=0),
                                 dict(members=65)])
 def test_unsupported_shapes_raise(kind, kw):
-    Pop, _, _ = _classes(kind)
+    Pop, _, _ = classes(kind)
     a = dict(members=2, state_dim=6, action_dim=3, hidden_dim=256)
     a.update(kw)
     with pytest.raises(ValueError):
@@ -292,8 +179,7 @@ def test_a_refused_call_leaves_every_counter_at_zero(algo):
     """A batch of 0 rows, which the workspace query refuses, and a `noise` of the wrong shape raise from `train` (DATD3 / DARC: from
     `update` too) before total_it or a step number moves -- in the single learner as in a population.  No device is touched."""
     from armenv.fused_td3 import FusedTD3
-    from armenv.fused_td3_pop import FusedTD3Population
-    Pop, Single = (FusedTD3Population, FusedTD3) if algo == "td3" else _classes(algo)[:2]
+    Pop, Single, _ = classes(algo)
     two_updates = algo in ("datd3", "darc")
     for learner, lead in ((Single(6, 3, 0.7, device="cpu"), ()), (Pop(2, 6, 3, 0.7, device="cpu"), (2,))):
         def batch(B):
@@ -332,18 +218,8 @@ def test_train_pop_refuses_an_unknown_agent():
         train_reach_population(members=1, iterations=0, algo="ddpg")
 
 
-@pytest.fixture(scope="module")
-def learner_kernels():
-    if not os.path.exists(isa.LIB):
-        pytest.skip("libarmenv.so is not built")
-    if not os.path.exists(os.path.join(isa.LLVM, "llvm-objdump")):
-        pytest.skip("the ROCm LLVM tools (llvm-objdump, llvm-readelf) are not installed")
-    rows = [r for r in isa.all_kernels() if "armenv::learner::" in r[1]]
-    return {dm.split("armenv::learner::")[1].split("(")[0]: (md, ins) for _, dm, md, ins in rows}
-
-
 def test_population_head_kernels_are_in_the_code_object(learner_kernels):
-    """test_td3_fused_host.py holds every armenv::learner:: kernel, these included, to no scratch, no atomics and exact f32; here:
+    """test_td3_fused_host.py holds all of learner_host.learner_kernels, these included, to no scratch, no atomics and exact f32; here:
     they exist, beside their single forms, and take the member from the grid's second dimension."""
     assert set(POP_KERNELS) <= set(learner_kernels), sorted(learner_kernels)
     assert {k.replace("_pop_kernel", "_kernel") for k in POP_KERNELS} <= set(learner_kernels)

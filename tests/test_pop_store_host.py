@@ -3,54 +3,25 @@ armenv_pop_write_episodes, include/armenv.h; armenv.replay.PopulationTrajectoryS
 argument is refused before any HIP call, the population kernels are in the built code object without scratch or LDS, and the stacked
 rings keep TrajectoryStore's books."""
 import ctypes as C
-import os
-import subprocess
-import sys
-import tempfile
 
 import pytest
 import torch
 
-from conftest import ROOT
+from learner_host import all_kernels, ctypes_layout, header_layout, refused as _refused
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
-import isa  # noqa: E402
-
-HEADER_DIR = os.path.join(ROOT, "include")
-EINVAL = -1
 POINTERS = ("obs0_dev", "obs_after_dev", "next_obs_dev", "action_dev", "reward_dev", "done_dev", "episodes_dev", "num_episodes_dev",
             "states_dev", "actions_dev", "next_states_dev", "rewards_dev", "dones_dev")
 
 
 # ------------------------------------------------------------------------------------------------ H1: ABI layout
 
-def _ctypes_layout(struct, prefix=""):
-    out = []
-    for name, typ in struct._fields_:
-        off = getattr(struct, name).offset
-        if isinstance(typ, type) and issubclass(typ, C.Structure):
-            out += [(f"{prefix}{name}.{k}", off + o) for k, o in _ctypes_layout(typ, "")]
-        else:
-            out.append((prefix + name, off))
-    return out
-
-
 def test_struct_layout_matches_the_header():
     from armenv import _lib as L
-    members = _ctypes_layout(L.ArmEnvHerPopArgs)
+    members = ctypes_layout(L.ArmEnvHerPopArgs)
     assert [m for m, _ in members][-2:] == ["members", "episodes_stride"] and ("one.picks_out_dev", L.ArmEnvHerArgs.picks_out_dev.offset) in members
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "armenv.h"', "int main(void) {",
-             '  printf("%zu %zu\\n", sizeof(ArmEnvHerPopArgs), sizeof(ArmEnvHerArgs));']
-    lines += ['  printf("%%zu\\n", offsetof(ArmEnvHerPopArgs, %s));' % m for m, _ in members]
-    lines += ["  return 0;", "}"]
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        with open(src, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
-        subprocess.run(["gcc", "-std=c99", "-Wall", "-I", HEADER_DIR, "-o", exe, src], check=True)
-        out = subprocess.run([exe], check=True, stdout=subprocess.PIPE, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(L.ArmEnvHerPopArgs) and int(out[1]) == C.sizeof(L.ArmEnvHerArgs)
-    assert [int(x) for x in out[2:]] == [o for _, o in members], members
+    sizes, offsets = header_layout(L.ArmEnvHerPopArgs, extra=("sizeof(ArmEnvHerArgs)",))
+    assert sizes == [C.sizeof(L.ArmEnvHerPopArgs), C.sizeof(L.ArmEnvHerArgs)]
+    assert offsets == [o for _, o in members], members
     assert L.ArmEnvHerPopArgs.members.offset == C.sizeof(L.ArmEnvHerArgs)
 
 
@@ -76,15 +47,6 @@ def _args(P=3, B=64, D=6):
     for k, name in enumerate(POINTERS):
         setattr(a, name, 0x10000000 + 0x1000000 * k)
     return pa
-
-
-def _refused(fn, *args):
-    from armenv import _lib as L
-    lib = L.load()
-    rc, msg = getattr(lib, fn)(*args), lib.armenv_last_error().decode()
-    assert rc == EINVAL, (rc, msg)                       # ARMENV_EINVAL, not ENODEV: nothing touched the device
-    assert msg.startswith(fn), msg
-    return msg
 
 
 def _one(field, value):
@@ -159,11 +121,7 @@ def test_bad_write_arguments_are_refused_before_any_device_call(field, change):
 
 @pytest.fixture(scope="module")
 def store_kernels():
-    if not os.path.exists(isa.LIB):
-        pytest.skip("libarmenv.so is not built")
-    if not os.path.exists(os.path.join(isa.LLVM, "llvm-objdump")):
-        pytest.skip("the ROCm LLVM tools (llvm-objdump, llvm-readelf) are not installed")
-    return {dm.replace("void ", "").split("(")[0].replace("armenv::", ""): (md, ins) for _, dm, md, ins in isa.all_kernels()
+    return {dm.replace("void ", "").split("(")[0].replace("armenv::", ""): (md, ins) for _, dm, md, ins in all_kernels()
             if "her_sample" in dm or "index_episodes" in dm}
 
 

@@ -2,52 +2,22 @@
 header, the workspace query is P single workspaces, every argument is validated before any HIP call, FusedTD3Population's stacks
 hold what P seeded FusedTD3 learners hold, and the population kernels are in the built code object."""
 import ctypes as C
-import os
-import subprocess
-import sys
-import tempfile
 
 import pytest
 import torch
 
-from conftest import ROOT
+from learner_host import POP_REFUSALS, TD3_NETS as NETS, ctypes_layout, fake_pop_args, header_layout, learner_kernels, refused  # noqa: F401
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
-import isa  # noqa: E402
-
-HEADER_DIR = os.path.join(ROOT, "include")
 POP_KERNELS = ("gemm_pop_kernel", "actor_head_pop_kernel", "critic_head_pop_kernel", "actor_back_pop_kernel", "adam_pop_kernel")
-NETS = ("actor", "q1", "q2", "target_actor", "target_q1", "target_q2", "actor_m", "actor_v", "q1_m", "q1_v", "q2_m", "q2_v")
-
-
-def _ctypes_layout(struct, prefix=""):
-    """[(C member path, offset)] of every scalar member of a ctypes struct, nested structs flattened"""
-    out = []
-    for name, typ in struct._fields_:
-        off = getattr(struct, name).offset
-        if isinstance(typ, type) and issubclass(typ, C.Structure):
-            out += [(f"{prefix}{name}.{k}", off + o) for k, o in _ctypes_layout(typ, "")]
-        else:
-            out.append((prefix + name, off))
-    return out
 
 
 def test_struct_layout_matches_the_header():
     from armenv import _lib as L
-    members = _ctypes_layout(L.ArmEnvTd3PopArgs)
+    members = ctypes_layout(L.ArmEnvTd3PopArgs)
     assert ("members", L.ArmEnvTd3PopArgs.members.offset) in members and any(m.startswith("one.q2_v.") for m, _ in members)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "armenv.h"', "int main(void) {",
-             '  printf("%zu %zu\\n", sizeof(ArmEnvTd3PopArgs), sizeof(ArmEnvTd3Args));']
-    lines += ['  printf("%%zu\\n", offsetof(ArmEnvTd3PopArgs, %s));' % m for m, _ in members]
-    lines += ["  return 0;", "}"]
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
-        with open(src, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
-        subprocess.run(["gcc", "-std=c99", "-Wall", "-I", HEADER_DIR, "-o", exe, src], check=True)
-        out = subprocess.run([exe], check=True, stdout=subprocess.PIPE, text=True).stdout.split()
-    assert int(out[0]) == C.sizeof(L.ArmEnvTd3PopArgs) and int(out[1]) == C.sizeof(L.ArmEnvTd3Args)
-    assert [int(x) for x in out[2:]] == [o for _, o in members], members
+    sizes, offsets = header_layout(L.ArmEnvTd3PopArgs, extra=("sizeof(ArmEnvTd3Args)",))
+    assert sizes == [C.sizeof(L.ArmEnvTd3PopArgs), C.sizeof(L.ArmEnvTd3Args)]
+    assert offsets == [o for _, o in members], members
 
 
 def test_the_abi_version_did_not_move():
@@ -75,61 +45,17 @@ def test_population_workspace_refuses_unsupported_sizes():
     assert lib.armenv_td3_pop_workspace_bytes(6, 256, 0, 2) == -1
 
 
-def _args(P=3, B=64, D=6):
-    """Arguments that pass every check but the one a test breaks: fake (never dereferenced) 16-byte aligned device pointers.
-    NOT to be passed unmodified -- a valid set would be enqueued."""
-    from armenv import _lib as L
-    pa = L.ArmEnvTd3PopArgs()
-    pa.members = P
-    a = pa.one
-    a.device, a.state_dim, a.action_dim, a.hidden_dim, a.batch = 0, D, 3, 256, B
-    a.action_bound, a.gamma, a.tau, a.policy_noise, a.noise_clip = 0.7, 0.98, 0.005, 0.2, 0.5
-    a.actor_lr, a.critic_lr, a.beta1, a.beta2, a.eps = 1e-3, 1e-3, 0.9, 0.999, 1e-8
-    a.critic_step, a.actor_step, a.with_actor = 1, 1, 1
-    addr = [0x10000000]
-
-    def ptr():
-        addr[0] += 0x1000000
-        return addr[0]
-    for net in NETS:
-        m = getattr(a, net)
-        for k in ("W1", "b1", "W2", "b2", "W3", "b3"):
-            setattr(m, k, ptr())
-    for k in ("states_dev", "actions_dev", "next_states_dev", "rewards_dev", "dones_dev", "workspace_dev"):
-        setattr(a, k, ptr())
-    a.workspace_bytes = L.load().armenv_td3_pop_workspace_bytes(D, 256, B, P)
-    assert a.workspace_bytes > 0
-    return pa
-
-
-def _one(field, value):
-    return lambda pa: setattr(pa.one, field, value)
-
-
-@pytest.mark.parametrize("field,mutate", [
-    ("members", lambda pa: setattr(pa, "members", 0)),
-    ("members", lambda pa: setattr(pa, "members", 65)),
-    ("target_q2", lambda pa: setattr(pa.one.target_q2, "W2", None)),
-    ("states_dev", _one("states_dev", None)),
-    ("workspace_bytes", lambda pa: setattr(pa.one, "workspace_bytes", pa.one.workspace_bytes - 1)),
-    ("gamma", _one("gamma", float("nan"))),
-    ("batch", _one("batch", 0)),
-    ("hidden_dim", _one("hidden_dim", 128)),
-])
+@pytest.mark.parametrize("field,mutate", POP_REFUSALS["td3"])
 def test_bad_arguments_are_refused_before_any_device_call(field, mutate):
-    from armenv import _lib as L
-    lib = L.load()
-    pa = _args()
+    pa = fake_pop_args("td3")
     mutate(pa)
-    rc, msg = lib.armenv_td3_pop_update(C.byref(pa), None), lib.armenv_last_error().decode()
-    assert rc == -1, (rc, msg)                       # ARMENV_EINVAL, not ENODEV: nothing touched the device
-    assert field in msg and msg.startswith("armenv_td3_pop_update"), msg
+    assert field in refused("armenv_td3_pop_update", C.byref(pa), None)
 
 
 def test_a_single_workspace_is_too_small_for_a_population():
     from armenv import _lib as L
     lib = L.load()
-    pa = _args(P=2)
+    pa = fake_pop_args("td3", P=2)
     pa.one.workspace_bytes = lib.armenv_td3_workspace_bytes(6, 256, 64)
     rc, msg = lib.armenv_td3_pop_update(C.byref(pa), None), lib.armenv_last_error().decode()
     assert rc == -1 and "workspace_bytes" in msg and "armenv_td3_pop_workspace_bytes" in msg, msg
@@ -213,18 +139,8 @@ def test_unsupported_shapes_raise(kw):
         FusedTD3Population(a["members"], a["state_dim"], a["action_dim"], 0.7, hidden_dim=a["hidden_dim"], device="cpu")
 
 
-@pytest.fixture(scope="module")
-def learner_kernels():
-    if not os.path.exists(isa.LIB):
-        pytest.skip("libarmenv.so is not built")
-    if not os.path.exists(os.path.join(isa.LLVM, "llvm-objdump")):
-        pytest.skip("the ROCm LLVM tools (llvm-objdump, llvm-readelf) are not installed")
-    rows = [r for r in isa.all_kernels() if "armenv::learner::" in r[1]]
-    return {dm.split("armenv::learner::")[1].split("(")[0]: (md, ins) for _, dm, md, ins in rows}
-
-
 def test_population_kernels_are_in_the_code_object(learner_kernels):
-    """test_td3_fused_host.py holds every armenv::learner:: kernel, these included, to no scratch, no atomics and exact f32."""
+    """test_td3_fused_host.py holds all of learner_host.learner_kernels, these included, to no scratch, no atomics and exact f32."""
     assert set(POP_KERNELS) <= set(learner_kernels), sorted(learner_kernels)
     md, ins = learner_kernels["gemm_pop_kernel"]
     assert "v_mfma_f32_32x32x2_f32" in [i.mnem for i in ins]

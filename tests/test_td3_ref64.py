@@ -41,26 +41,9 @@ def test_reference_reproduces_the_golden_updates():
             assert np.abs(v.numpy() - ref).max() < 1e-5, (name, k, np.abs(v.numpy() - ref).max())
 
 
-def _batch(gen, B, D, done_p=0.3):
-    return dict(states=torch.rand(B, D, generator=gen, dtype=torch.float64),
-                actions=torch.rand(B, 3, generator=gen, dtype=torch.float64) * 0.5 - 0.25,
-                next_states=torch.rand(B, D, generator=gen, dtype=torch.float64),
-                rewards=torch.rand(B, generator=gen, dtype=torch.float64) - 0.5,
-                dones=(torch.rand(B, generator=gen, dtype=torch.float64) < done_p).to(torch.float64))
-
-
 def _torch_state(t):
-    ms = {}
-    for which, net, opt in (("actor", t.actor, t.actor_opt), ("critic", t.critic, t.critic_opt)):
-        m, v, step = [], [], 0
-        for p in net.parameters():
-            s = opt.state.get(p, {})
-            m.append(s["exp_avg"] if "exp_avg" in s else torch.zeros_like(p))
-            v.append(s["exp_avg_sq"] if "exp_avg_sq" in s else torch.zeros_like(p))
-            step = int(s["step"]) if "step" in s else 0
-        ms[which] = (m, v, step)
-    return R.state_from(t.actor, t.critic, t.target_actor, t.target_critic, ms["actor"][0], ms["actor"][1], ms["critic"][0],
-                        ms["critic"][1], ms["actor"][2], ms["critic"][2])
+    (am, av, a_step), (cm, cv, c_step) = R.adam_state(t.actor, t.actor_opt), R.adam_state(t.critic, t.critic_opt)
+    return R.state_from(t.actor, t.critic, t.target_actor, t.target_critic, am, av, cm, cv, a_step, c_step)
 
 
 def _autograd_case(B, D, with_actor, seed, monkeypatch, hp, target_actor_gain=1.0):
@@ -85,9 +68,9 @@ def _autograd_case(B, D, with_actor, seed, monkeypatch, hp, target_actor_gain=1.
         finally:
             monkeypatch.undo()
     for _ in range(2):
-        update(_batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64), True)
+        update(R.random_batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64), True)
     st = _torch_state(t)
-    batch, noise = _batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64)
+    batch, noise = R.random_batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64)
     loss = float(update(batch, noise, with_actor))
     return st, batch, noise, t, loss
 
@@ -207,7 +190,9 @@ def test_workspace_query_at_the_batch_limit():
 
 
 def test_update_refuses_a_batch_above_the_limit():
-    import test_td3_fused_host as H
     from armenv import _lib as L
-    rc, msg = H._breaks(lambda a: setattr(a, "batch", 2 ** 20 + 1))
+    from learner_host import fake_args
+    lib, a = L.load(), fake_args("td3")
+    a.batch = 2 ** 20 + 1
+    rc, msg = lib.armenv_td3_update(C.byref(a), None), lib.armenv_last_error().decode()
     assert rc == -1 and "batch" in msg and "armenv_td3_update" in msg, (rc, msg)
