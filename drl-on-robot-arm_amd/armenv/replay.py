@@ -1,9 +1,16 @@
-"""Device-resident trajectory store with the reference's HER-"future" sampling
-(/root/reference/utils/rl_utils.py:91-199: Trajectory, ReplayBuffer_Trajectory_reach / _push), fed directly by the
-[T, N, ...] tensors a rollout produces.  Nothing leaves HBM: episodes are indexed and batches are gathered by HIP
-kernels behind the C ABI (armenv_count_episodes / armenv_write_episodes / armenv_her_sample).  ``PopulationTrajectoryStore`` is the
-store of P members trained side by side (armenv.train_pop): P stacked rings of one geometry, indexed and sampled in one launch each
-(armenv_pop_count_episodes / armenv_pop_write_episodes / armenv_her_pop_sample)."""
+"""Device-resident trajectory store with the reference's HER-"future" sampling (the reference's utils/rl_utils.py:91-199:
+Trajectory, ReplayBuffer_Trajectory_reach / _push), fed directly by the [T, N, ...] tensors a rollout produces.  Nothing leaves HBM:
+episodes are indexed and batches are gathered by HIP kernels behind the C ABI.
+
+The store is written once, in ``_Store``: the ring and its allocation, the append (``ring_append`` and the segment copies), the
+episode index (count, cumsum, write), the sampler's argument struct and ``sample``.  Every tensor carries the leading shape ``_lead``
+in front, so the time axis of a ring is ``len(_lead)``.  Two thin classes set ``_lead`` and name the three C calls:
+
+  TrajectoryStore             _lead = ()     armenv_count_episodes / armenv_write_episodes / armenv_her_sample
+  PopulationTrajectoryStore   _lead = (P,)   armenv_pop_count_episodes / armenv_pop_write_episodes / armenv_her_pop_sample
+
+The population store (armenv.train_pop) indexes and samples all P members in one launch each.  The single store keeps its own entry
+points and kernels: they are what the population kernels are proven against, bit for bit."""
 import ctypes as C
 
 import torch
@@ -19,7 +26,7 @@ def ring_append(cap, base, T, at_reset, Tc):
     """The ring arithmetic of appending a chunk of ``Tc`` steps to a window of ``T`` logical steps that starts at physical row
     ``base`` of ``cap`` rows: the oldest steps that no longer fit fall out (the window then starts mid-episode).  Returns
     (base, T, at_reset, segments) after the append; segments = [(ring row, chunk row, rows)], one entry, or two where the chunk
-    wraps.  The one copy of this arithmetic: TrajectoryStore and PopulationTrajectoryStore both call it."""
+    wraps."""
     drop = max(0, T + Tc - cap)                            # oldest steps that fall out of the window
     if drop:
         base = (base + drop) % cap
@@ -35,7 +42,7 @@ def ring_append(cap, base, T, at_reset, Tc):
 
 class Trajectory:
     """One episode collected step by step on the host, as the reference's single-env loops do
-    (/root/reference/utils/rl_utils.py:91-105, call sites main.py:109,128): ``Trajectory(init_state)``,
+    (utils/rl_utils.py:91-105, call sites main.py:109,128): ``Trajectory(init_state)``,
     ``store_step(action, state, reward, done)``; handed to ``TrajectoryStore.add_trajectory``."""
 
     def __init__(self, init_state):
@@ -53,22 +60,175 @@ class Trajectory:
         self.length += 1
 
 
-class TrajectoryStore:
+# ring tensor <- the key of the rollout's output dict that feeds it (BatchedEnv.bind_rollout's names)
+_RING_SOURCES = dict(obs_after="obs", next_obs="terminal_obs", action="actions", reward="reward", done="done_u8")
+_BATCH_KEYS = ("states", "actions", "next_states", "rewards", "dones")
+
+
+class _Store:
+    """What TrajectoryStore and PopulationTrajectoryStore share -- everything but the three C calls (``_count``, ``_write``,
+    ``_launch``) and how rollouts reach ``_append``.  ``_ring`` is the ring dict: the geometry (cap, base, T, N, D, at_reset), obs0,
+    the five rings [cap][N][...] and the index (counts, offsets, episodes, num_episodes), every tensor with ``_lead`` in front."""
+
+    _lead = ()
+
+    def __init__(self, device, seed, capacity_steps):
+        self.device, self.seed, self.capacity = torch.device(device), int(seed), capacity_steps
+        self._lib = L.load()
+        self._draw = 0
+        self._ring = None
+        self._bound = None             # (key, out, ArmEnvHerPopArgs) of the last ``sample``; dropped whenever the ring or its index moves
+        self._started = False          # the first append has stored obs0
+
+    @property
+    def chunk(self):
+        """None before the first add, then the indexed ring dict.  Assignable: a store adopts another's ring
+        (``PopulationTrajectoryStore.member_view``) this way."""
+        return self._ring
+
+    @chunk.setter
+    def chunk(self, ring):
+        self._ring, self._bound = ring, None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _new(self, shape, dtype):
+        return torch.zeros(self._lead + shape, dtype=dtype, device=self.device)
+
+    def _index_buffers(self, cap, N):
+        return dict(counts=self._new((N,), torch.int32), offsets=self._new((N,), torch.int64),
+                    episodes=self._new((cap * N, 3), torch.int32),                                   # bound: one per step
+                    num_episodes=self._new((), torch.int64))
+
+    def _allocate(self, N, D):
+        """an empty ring of ``capacity`` steps of N envs with D observations (no row outside the window is ever read)"""
+        cap, f32 = int(self.capacity), torch.float32
+        self.chunk = dict(cap=cap, base=0, T=0, N=N, D=D, at_reset=True, obs0=self._new((N, D), f32),
+                          obs_after=self._new((cap, N, D), f32), next_obs=self._new((cap, N, D), f32),
+                          action=self._new((cap, N, 3), f32), reward=self._new((cap, N), f32),
+                          done=self._new((cap, N), torch.uint8), **self._index_buffers(cap, N))
+        return self._ring
+
+    def _append(self, src, obs0, starts_at_reset):
+        """Appends the chunk ``src`` (ring key -> tensor ``_lead`` + [Tc][N][...]) to the ring, allocated on the first call, and
+        indexes it: the oldest steps fall out.  ``obs0`` and ``starts_at_reset`` are read by the first call only (later windows start
+        at rows the ring holds)."""
+        ax = len(self._lead)
+        Tc, N, D = src["obs_after"].shape[ax:]
+        r = self._ring
+        if r is None:
+            if int(self.capacity) < Tc:
+                raise ValueError("capacity_steps smaller than one rollout chunk")
+            r = self._allocate(N, D)
+        elif (r["N"], r["D"]) != (N, D):
+            raise ValueError("%s: the chunk's [N][D] changed" % type(self).__name__)
+        if not self._started:
+            r["obs0"].copy_(obs0)
+            r["at_reset"] = bool(starts_at_reset)
+            self._started = True
+        r["base"], r["T"], r["at_reset"], segments = ring_append(r["cap"], r["base"], r["T"], r["at_reset"], Tc)
+        for k, v in src.items():
+            for row, at, rows in segments:
+                r[k].narrow(ax, row, rows).copy_(v.narrow(ax, at, rows))
+        self._index()
+
+    def _index(self):
+        """The episode index of the window: count per env, cumsum within each member, write, num_episodes.  A ring that came without
+        an index (a view another store handed over) gets its own buffers."""
+        r = self._ring
+        if "episodes" not in r:
+            r.update(self._index_buffers(r["cap"], r["N"]))
+        dev, stream = self.device.index or 0, self._stream()
+        geometry = (r["T"], r["N"], r["base"], r["cap"], _p(r["done"]), int(r["at_reset"]), _p(r["counts"]))
+        L.check(self._count(dev, geometry, stream))
+        torch.cumsum(r["counts"], -1, dtype=torch.int64, out=r["offsets"])
+        L.check(self._write(dev, geometry, _p(r["offsets"]), r["episodes"], stream))
+        last = r["offsets"][..., -1]                              # i64 _lead: contiguous as it stands where there is one member
+        r["num_episodes"] = last if last.is_contiguous() else r["num_episodes"].copy_(last)
+        self.chunk = r                                            # T and base moved: the binding goes
+
+    def _batch_spec(self, B):
+        """key -> (shape, dtype) of a batch of B rows"""
+        lead, D, f32 = self._lead, self._ring["D"], torch.float32
+        return dict(states=(lead + (B, D), f32), actions=(lead + (B, 3), f32), next_states=(lead + (B, D), f32),
+                    rewards=(lead + (B,), f32), dones=(lead + (B,), torch.uint8))
+
+    def _bind(self, B, use_her, dis_threshold, her_ratio, out):
+        """the sampler's argument struct over the ring and ``out``, everything but `draw` and the two picks pointers; its ``.one`` is
+        the ArmEnvHerArgs of the single call"""
+        r, lead, dev, D = self._ring, self._lead, self.device, self._ring["D"]
+        for k, (shape, dt) in self._batch_spec(B).items():
+            t = out[k]
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{type(self).__name__}.sample: out[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {dev}")
+        args = L.ArmEnvHerPopArgs()
+        args.members, args.episodes_stride = (lead or (1,))[0], r["episodes"].shape[-2]
+        a = args.one
+        a.T, a.N, a.ring_base, a.ring_cap, a.obs_dim, a.use_her = r["T"], r["N"], r["base"], r["cap"], D, int(bool(use_her))
+        a.obs0_dev, a.obs_after_dev, a.next_obs_dev = r["obs0"].data_ptr(), r["obs_after"].data_ptr(), r["next_obs"].data_ptr()
+        a.action_dev, a.reward_dev, a.done_dev = r["action"].data_ptr(), r["reward"].data_ptr(), r["done"].data_ptr()
+        a.episodes_dev, a.num_episodes_dev = r["episodes"].data_ptr(), r["num_episodes"].data_ptr()
+        a.batch, a.seed = B, self.seed & 0xFFFFFFFFFFFFFFFF
+        a.her_ratio, a.dis_threshold = float(her_ratio), float(dis_threshold)
+        a.states_dev, a.actions_dev, a.next_states_dev = out["states"].data_ptr(), out["actions"].data_ptr(), out["next_states"].data_ptr()
+        a.rewards_dev, a.dones_dev = out["rewards"].data_ptr(), out["dones"].data_ptr()
+        return args
+
+    def sample(self, batch_size, use_her=True, dis_threshold=0.1, her_ratio=0.8, picks=None, return_picks=False, out=None):
+        """A batch of B = ``batch_size`` rows (of every member, in one launch) under the reference's keys, as device tensors
+        ``_lead`` + [B][...].  ``out`` (optional): a dict of preallocated tensors under the same keys (``batch_buffers`` of a fused
+        learner or population, the static buffers of ``TD3.capture``); the batch is then written in place and no memory is allocated.
+        ``picks`` i32 ``_lead`` + [B][4]: teacher-forced draws.  ``return_picks``: ``out["picks"]`` i32 ``_lead`` + [B][4]; a tensor
+        of that kind already in ``out`` is written in place, by both stores.  The argument struct is built once per (``out``,
+        settings, state of the ring); later calls only refresh `draw` and the two picks pointers."""
+        if self._ring is None:
+            raise RuntimeError("%s.sample: no rollout stored" % type(self).__name__)
+        lead, B, dev = self._lead, int(batch_size), self.device
+        if out is None:
+            out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in self._batch_spec(B).items()}
+        key = (B, bool(use_her), float(dis_threshold), float(her_ratio)) + tuple(out[k].data_ptr() for k in _BATCH_KEYS)
+        bound = self._bound
+        if bound is not None and bound[0] == key and bound[1] is out:
+            args = bound[2]
+        else:
+            args = self._bind(B, use_her, dis_threshold, her_ratio, out)
+            self._bound = (key, out, args)                        # holds `out`: the pointers in `args` stay valid
+        a = args.one
+        pk = None
+        if picks is not None:
+            pk = torch.as_tensor(picks).to(device=dev, dtype=torch.int32).contiguous()
+            assert tuple(pk.shape) == lead + (B, 4)
+        a.picks_dev = None if pk is None else pk.data_ptr()
+        if return_picks:
+            t = out.get("picks")
+            if t is None or tuple(t.shape) != lead + (B, 4) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                out["picks"] = torch.empty(lead + (B, 4), dtype=torch.int32, device=dev)
+        a.picks_out_dev = out["picks"].data_ptr() if return_picks else None
+        a.draw = self._draw
+        self._draw += 1
+        L.check(self._launch(dev.index or 0, args, self._stream()))
+        if pk is not None:
+            torch.cuda.current_stream(dev).synchronize()
+        return out
+
+
+class TrajectoryStore(_Store):
     """A time-major ring of the last ``capacity_steps`` env steps of N envs (the reference's deque keeps the last
     `capacity` trajectories, rl_utils.py:109-113).  ``size()`` = number of complete episodes currently in the window;
     ``sample(batch_size, use_her, dis_threshold, her_ratio)`` returns device tensors under the reference's keys."""
 
     def __init__(self, device="cuda:0", seed=0, capacity_steps=None):
-        self.device = torch.device(device)
-        self._lib = L.load()
-        self.seed = int(seed)
-        self._draw = 0
-        self.capacity = capacity_steps
-        self.chunk = None
-        self._ring = None
+        super().__init__(device, seed, capacity_steps)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _count(self, dev, geometry, stream):
+        return self._lib.armenv_count_episodes(dev, *geometry, stream)
+
+    def _write(self, dev, geometry, offsets, episodes, stream):
+        return self._lib.armenv_write_episodes(dev, *geometry, offsets, _p(episodes), stream)
+
+    def _launch(self, dev, args, stream):
+        return self._lib.armenv_her_sample(dev, C.byref(args.one), stream)
 
     def add_rollout(self, obs0, out, actions=None, starts_at_reset=True):
         """Append a rollout chunk.  obs0: observation [N, D] before the chunk's first step (only used when the window
@@ -77,24 +237,11 @@ class TrajectoryStore:
         this chunk (zero-copy); with it, chunks accumulate in a ring and the oldest steps fall out."""
         acts = actions if actions is not None else out["actions"]
         src = dict(obs_after=out["obs"], next_obs=out["terminal_obs"], action=acts, reward=out["reward"], done=out["done_u8"])
+        if self.capacity is not None:
+            return self._append(src, obs0, starts_at_reset)
         Tc, N, D = src["obs_after"].shape
-        if self.capacity is None:
-            self._ring = dict(cap=Tc, base=0, T=Tc, N=N, D=D, obs0=obs0.contiguous(), at_reset=bool(starts_at_reset),
-                              **{k: v.contiguous() for k, v in src.items()})
-        else:
-            r = self._ring
-            if r is None:
-                cap = int(self.capacity)
-                if cap < Tc:
-                    raise ValueError("capacity_steps smaller than one rollout chunk")
-                r = dict(cap=cap, base=0, T=0, N=N, D=D, obs0=obs0.clone(), at_reset=bool(starts_at_reset))
-                for k, v in src.items():
-                    r[k] = torch.empty((cap,) + tuple(v.shape[1:]), dtype=v.dtype, device=self.device)
-                self._ring = r
-            r["base"], r["T"], r["at_reset"], segments = ring_append(r["cap"], r["base"], r["T"], r["at_reset"], Tc)
-            for k, v in src.items():
-                for row, at, rows in segments:
-                    r[k][row:row + rows].copy_(v[at:at + rows])
+        self.chunk = dict(cap=Tc, base=0, T=Tc, N=N, D=D, obs0=obs0.contiguous(), at_reset=bool(starts_at_reset),
+                          **{k: v.contiguous() for k, v in src.items()})
         self._index()
 
     def add_trajectory(self, traj):
@@ -125,76 +272,12 @@ class TrajectoryStore:
             r["obs_after"][(r["base"] + r["T"] - 1) % r["cap"], 0].copy_(st[0])
         self.add_rollout(st[0:1].contiguous(), out, actions=acts, starts_at_reset=first)
 
-    def _index(self):
-        r = self._ring
-        dev = self.device.index or 0
-        T, N = r["T"], r["N"]
-        counts = torch.empty(N, dtype=torch.int32, device=self.device)
-        L.check(self._lib.armenv_count_episodes(dev, T, N, r["base"], r["cap"], _p(r["done"]), int(r["at_reset"]), _p(counts),
-                                                self._stream()))
-        offsets = torch.cumsum(counts, 0, dtype=torch.int64)
-        if r.get("episodes") is None or r["episodes"].shape[0] < T * N:
-            r["episodes"] = torch.empty((r["cap"] * N, 3), dtype=torch.int32, device=self.device)   # bound: one per step
-        L.check(self._lib.armenv_write_episodes(dev, T, N, r["base"], r["cap"], _p(r["done"]), int(r["at_reset"]), _p(counts),
-                                                _p(offsets), _p(r["episodes"]), self._stream()))
-        r["num_episodes"] = offsets[-1:].contiguous()
-        self.chunk = r
-
     def size(self):
         """number of complete episodes in the window (host sync)"""
-        return 0 if self.chunk is None else int(self.chunk["num_episodes"].item())
-
-    def sample(self, batch_size, use_her=True, dis_threshold=0.1, her_ratio=0.8, picks=None, return_picks=False, out=None):
-        """`out` (optional): dict of preallocated tensors under the same keys (e.g. the static buffers of
-        ``TD3.capture``); the batch is then written in place and no memory is allocated."""
-        ch = self.chunk
-        if ch is None:
-            raise RuntimeError("TrajectoryStore.sample: no rollout stored")
-        B, D, dev = int(batch_size), ch["D"], self.device
-        a = L.ArmEnvHerArgs()
-        a.T, a.N, a.ring_base, a.ring_cap, a.obs_dim, a.use_her = ch["T"], ch["N"], ch["base"], ch["cap"], D, int(bool(use_her))
-        a.obs0_dev, a.obs_after_dev, a.next_obs_dev = ch["obs0"].data_ptr(), ch["obs_after"].data_ptr(), ch["next_obs"].data_ptr()
-        a.action_dev, a.reward_dev, a.done_dev = ch["action"].data_ptr(), ch["reward"].data_ptr(), ch["done"].data_ptr()
-        a.episodes_dev, a.num_episodes_dev = ch["episodes"].data_ptr(), ch["num_episodes"].data_ptr()
-        a.batch = B
-        pk = None
-        if picks is not None:
-            pk = torch.as_tensor(picks).to(device=dev, dtype=torch.int32).contiguous()
-            assert tuple(pk.shape) == (B, 4)
-            a.picks_dev = pk.data_ptr()
-        a.seed, a.draw = self.seed, self._draw
-        self._draw += 1
-        a.her_ratio, a.dis_threshold = float(her_ratio), float(dis_threshold)
-        if out is None:
-            out = dict(states=torch.empty((B, D), dtype=torch.float32, device=dev),
-                       actions=torch.empty((B, 3), dtype=torch.float32, device=dev),
-                       next_states=torch.empty((B, D), dtype=torch.float32, device=dev),
-                       rewards=torch.empty(B, dtype=torch.float32, device=dev),
-                       dones=torch.empty(B, dtype=torch.uint8, device=dev))
-        else:
-            want = dict(states=((B, D), torch.float32), actions=((B, 3), torch.float32), next_states=((B, D), torch.float32),
-                        rewards=((B,), torch.float32), dones=((B,), torch.uint8))
-            for k, (shape, dt) in want.items():
-                t = out[k]
-                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
-                    raise ValueError(f"TrajectoryStore.sample: out[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {dev}")
-        a.states_dev, a.actions_dev, a.next_states_dev = out["states"].data_ptr(), out["actions"].data_ptr(), out["next_states"].data_ptr()
-        a.rewards_dev, a.dones_dev = out["rewards"].data_ptr(), out["dones"].data_ptr()
-        if return_picks:
-            out["picks"] = torch.empty((B, 4), dtype=torch.int32, device=dev)
-            a.picks_out_dev = out["picks"].data_ptr()
-        L.check(self._lib.armenv_her_sample(dev.index or 0, C.byref(a), self._stream()))
-        if pk is not None:
-            torch.cuda.current_stream(dev).synchronize()
-        return out
+        return 0 if self._ring is None else int(self._ring["num_episodes"].item())
 
 
-# ring tensor <- the key of the rollout's output dict that feeds it (BatchedEnv.bind_rollout's names)
-_RING_SOURCES = dict(obs_after="obs", next_obs="terminal_obs", action="actions", reward="reward", done="done_u8")
-_BATCH_KEYS = ("states", "actions", "next_states", "rewards", "dones")
-
-
-class PopulationTrajectoryStore:
+class PopulationTrajectoryStore(_Store):
     """The trajectory stores of P members that run in lockstep (armenv.train_pop): P rings of one geometry, stacked
     [P][capacity_steps][N][...], with one episode index [P][capacity_steps * N][3] and one count i64 [P].  The members' rollouts write
     straight into the store's staging block (``rollout_buffers``); ``add_rollouts`` moves it into the rings and indexes every member,
@@ -207,80 +290,39 @@ class PopulationTrajectoryStore:
             raise ValueError("PopulationTrajectoryStore: members must be 1..64")
         if capacity_steps is None or int(capacity_steps) < 1:
             raise ValueError("PopulationTrajectoryStore: capacity_steps (the rows of every member's ring) is required")
-        self.members, self.device, self.seed = int(members), torch.device(device), int(seed)
-        self.capacity = int(capacity_steps)
-        self._lib = L.load()
-        self._draw = 0
+        super().__init__(device, seed, int(capacity_steps))
+        self.members = int(members)
+        self._lead = (self.members,)
         self._staging = None
-        self._ring = None              # dict(cap, base, T, N, D, at_reset, obs0, the five rings, counts, offsets, episodes, num_episodes)
-        self._bound = None             # (key, out, ArmEnvHerPopArgs) of the last ``sample``
-        self._started = False          # the first add_rollouts has stored obs0
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _count(self, dev, geometry, stream):
+        return self._lib.armenv_pop_count_episodes(dev, self.members, *geometry, stream)
+
+    def _write(self, dev, geometry, offsets, episodes, stream):
+        return self._lib.armenv_pop_write_episodes(dev, self.members, *geometry, offsets, _p(episodes), episodes.shape[1], stream)
+
+    def _launch(self, dev, args, stream):
+        return self._lib.armenv_her_pop_sample(dev, C.byref(args), stream)
 
     def rollout_buffers(self, steps, N, D):
         """P dicts, member p's being contiguous views [steps][N][...] into one stacked staging block [P][steps][N][...], under the
         keys ``BatchedEnv.bind_rollout`` looks up: pass member p's as ``out=`` and its rollout writes straight into the block."""
-        P, T, dev = self.members, int(steps), self.device
-        f32, u8 = torch.float32, torch.uint8
-        self._staging = dict(obs=torch.zeros((P, T, N, D), dtype=f32, device=dev), reward=torch.zeros((P, T, N), dtype=f32, device=dev),
-                             done_u8=torch.zeros((P, T, N), dtype=u8, device=dev), success_u8=torch.zeros((P, T, N), dtype=u8, device=dev),
-                             actions=torch.zeros((P, T, N, 3), dtype=f32, device=dev),
-                             terminal_obs=torch.zeros((P, T, N, D), dtype=f32, device=dev))
-        return [{k: t[p] for k, t in self._staging.items()} for p in range(P)]
-
-    def _allocate(self, N, D):
-        P, cap, dev = self.members, self.capacity, self.device
-        f32 = torch.float32
-        self._ring = dict(cap=cap, base=0, T=0, N=N, D=D, at_reset=True, obs0=torch.zeros((P, N, D), dtype=f32, device=dev),
-                          obs_after=torch.zeros((P, cap, N, D), dtype=f32, device=dev),
-                          next_obs=torch.zeros((P, cap, N, D), dtype=f32, device=dev),
-                          action=torch.zeros((P, cap, N, 3), dtype=f32, device=dev),
-                          reward=torch.zeros((P, cap, N), dtype=f32, device=dev),
-                          done=torch.zeros((P, cap, N), dtype=torch.uint8, device=dev),
-                          counts=torch.zeros((P, N), dtype=torch.int32, device=dev),
-                          offsets=torch.zeros((P, N), dtype=torch.int64, device=dev),
-                          episodes=torch.zeros((P, cap * N, 3), dtype=torch.int32, device=dev),     # bound: one per step
-                          num_episodes=torch.zeros(P, dtype=torch.int64, device=dev))
-        return self._ring
+        T, f32, u8 = int(steps), torch.float32, torch.uint8
+        self._staging = dict(obs=self._new((T, N, D), f32), reward=self._new((T, N), f32), done_u8=self._new((T, N), u8),
+                             success_u8=self._new((T, N), u8), actions=self._new((T, N, 3), f32), terminal_obs=self._new((T, N, D), f32))
+        return [{k: t[p] for k, t in self._staging.items()} for p in range(self.members)]
 
     def add_rollouts(self, obs0, starts_at_reset=True):
         """Appends the staging block -- every member's last rollout -- to the rings and indexes every member.  obs0 f32 [P][N][D]:
         the members' observations before the chunk's first step (read on the first call only: later windows start at rows the ring
-        holds).  ``TrajectoryStore.add_rollout``'s arithmetic, once for all members."""
+        holds)."""
         stage = self._staging
         if stage is None:
             raise RuntimeError("PopulationTrajectoryStore.add_rollouts: call rollout_buffers(steps, N, D) and roll out into them first")
-        P, Tc, N, D = stage["obs"].shape
-        r = self._ring
-        if r is None:
-            if self.capacity < Tc:
-                raise ValueError("capacity_steps smaller than one rollout chunk")
-            if tuple(obs0.shape) != (P, N, D):
-                raise ValueError("PopulationTrajectoryStore.add_rollouts: obs0 must be [%d][%d][%d]" % (P, N, D))
-            r = self._allocate(N, D)
-        elif (r["N"], r["D"]) != (N, D):
-            raise ValueError("PopulationTrajectoryStore.add_rollouts: the staging block's [N][D] changed")
-        if not self._started:
-            r["obs0"].copy_(obs0)
-            r["at_reset"] = bool(starts_at_reset)
-            self._started = True
-        r["base"], r["T"], r["at_reset"], segments = ring_append(r["cap"], r["base"], r["T"], r["at_reset"], Tc)
-        for k, src in _RING_SOURCES.items():
-            for row, at, rows in segments:
-                r[k][:, row:row + rows].copy_(stage[src][:, at:at + rows])
-        self._index()
-
-    def _index(self):
-        r = self._ring
-        dev, P, stream = self.device.index or 0, self.members, self._stream()
-        geometry = (dev, P, r["T"], r["N"], r["base"], r["cap"], _p(r["done"]), int(r["at_reset"]), _p(r["counts"]))
-        L.check(self._lib.armenv_pop_count_episodes(*geometry, stream))
-        torch.cumsum(r["counts"], 1, dtype=torch.int64, out=r["offsets"])
-        L.check(self._lib.armenv_pop_write_episodes(*geometry, _p(r["offsets"]), _p(r["episodes"]), r["episodes"].shape[1], stream))
-        r["num_episodes"].copy_(r["offsets"][:, -1])
-        self._bound = None                                    # T and base moved
+        P, _, N, D = stage["obs"].shape
+        if not self._started and tuple(obs0.shape) != (P, N, D):
+            raise ValueError("PopulationTrajectoryStore.add_rollouts: obs0 must be [%d][%d][%d]" % (P, N, D))
+        self._append({k: stage[name] for k, name in _RING_SOURCES.items()}, obs0, starts_at_reset)
 
     def sizes(self):
         """the members' numbers of complete episodes in the window: a list of P ints from one device-to-host transfer"""
@@ -299,63 +341,3 @@ class PopulationTrajectoryStore:
         view.update({k: r[k][p] for k in ("obs0", "episodes") + tuple(_RING_SOURCES)})
         view["num_episodes"] = r["num_episodes"][p:p + 1]
         return view
-
-    def _bind(self, B, use_her, dis_threshold, her_ratio, out):
-        r, P, D, dev = self._ring, self.members, self._ring["D"], self.device
-        want = dict(states=((P, B, D), torch.float32), actions=((P, B, 3), torch.float32), next_states=((P, B, D), torch.float32),
-                    rewards=((P, B), torch.float32), dones=((P, B), torch.uint8))
-        for k, (shape, dt) in want.items():
-            t = out[k]
-            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"PopulationTrajectoryStore.sample: out[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {dev}")
-        args = L.ArmEnvHerPopArgs()
-        args.members, args.episodes_stride = P, r["episodes"].shape[1]
-        a = args.one
-        a.T, a.N, a.ring_base, a.ring_cap, a.obs_dim, a.use_her = r["T"], r["N"], r["base"], r["cap"], D, int(bool(use_her))
-        a.obs0_dev, a.obs_after_dev, a.next_obs_dev = r["obs0"].data_ptr(), r["obs_after"].data_ptr(), r["next_obs"].data_ptr()
-        a.action_dev, a.reward_dev, a.done_dev = r["action"].data_ptr(), r["reward"].data_ptr(), r["done"].data_ptr()
-        a.episodes_dev, a.num_episodes_dev = r["episodes"].data_ptr(), r["num_episodes"].data_ptr()
-        a.batch, a.seed = B, self.seed & 0xFFFFFFFFFFFFFFFF
-        a.her_ratio, a.dis_threshold = float(her_ratio), float(dis_threshold)
-        a.states_dev, a.actions_dev, a.next_states_dev = out["states"].data_ptr(), out["actions"].data_ptr(), out["next_states"].data_ptr()
-        a.rewards_dev, a.dones_dev = out["rewards"].data_ptr(), out["dones"].data_ptr()
-        return args
-
-    def sample(self, batch_size, use_her=True, dis_threshold=0.1, her_ratio=0.8, out=None, picks=None, return_picks=False):
-        """Every member's batch in one launch, into ``out``: the stacked dict [P][B][...] of ``FusedPopulation.batch_buffers`` (None:
-        allocated here).  ``picks`` i32 [P][B][4]: teacher-forced draws; ``return_picks``: ``out["picks"]`` i32 [P][B][4] (a tensor of
-        that kind already in ``out`` is written in place).  The argument struct is built once per (``out``, settings,
-        ``add_rollouts``); later calls only refresh `draw` and the two picks pointers."""
-        if self._ring is None:
-            raise RuntimeError("PopulationTrajectoryStore.sample: no rollout stored")
-        P, B, D, dev = self.members, int(batch_size), self._ring["D"], self.device
-        if out is None:
-            out = dict(states=torch.empty((P, B, D), dtype=torch.float32, device=dev),
-                       actions=torch.empty((P, B, 3), dtype=torch.float32, device=dev),
-                       next_states=torch.empty((P, B, D), dtype=torch.float32, device=dev),
-                       rewards=torch.empty((P, B), dtype=torch.float32, device=dev),
-                       dones=torch.empty((P, B), dtype=torch.uint8, device=dev))
-        key = (B, bool(use_her), float(dis_threshold), float(her_ratio)) + tuple(out[k].data_ptr() for k in _BATCH_KEYS)
-        bound = self._bound
-        if bound is not None and bound[0] == key and bound[1] is out:
-            args = bound[2]
-        else:
-            args = self._bind(B, use_her, dis_threshold, her_ratio, out)
-            self._bound = (key, out, args)                    # holds `out`: the pointers in `args` stay valid
-        a = args.one
-        pk = None
-        if picks is not None:
-            pk = torch.as_tensor(picks).to(device=dev, dtype=torch.int32).contiguous()
-            assert tuple(pk.shape) == (P, B, 4)
-        a.picks_dev = None if pk is None else pk.data_ptr()
-        if return_picks:
-            t = out.get("picks")
-            if t is None or tuple(t.shape) != (P, B, 4) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
-                out["picks"] = torch.empty((P, B, 4), dtype=torch.int32, device=dev)
-        a.picks_out_dev = out["picks"].data_ptr() if return_picks else None
-        a.draw = self._draw
-        self._draw += 1
-        L.check(self._lib.armenv_her_pop_sample(dev.index or 0, C.byref(args), self._stream()))
-        if pk is not None:
-            torch.cuda.current_stream(dev).synchronize()
-        return out

@@ -594,29 +594,6 @@ int armenv_rollout(ArmEnv *env, int32_t steps, const float *actions_dev, float *
   DeviceGuard guard_(device);                                                          \
   if (!guard_.ok) return fail(ARMENV_ENODEV, "%s: hipSetDevice(%d) failed", __func__, (int)(device))
 
-int armenv_count_episodes(int32_t device, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap, const uint8_t *done_dev,
-                          int32_t starts_at_reset, int32_t *counts_dev, void *stream) {
-  DEV_ENTER(device);
-  if (T < 0 || N < 1 || ring_cap < T || ring_cap < 1 || ring_base < 0 || !done_dev || !counts_dev)
-    return fail(ARMENV_EINVAL, "armenv_count_episodes: bad arguments");
-  hipLaunchKernelGGL(index_episodes_kernel, dim3(grid_for(N, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), T, N,
-                     ring_base, ring_cap, done_dev, starts_at_reset, counts_dev, (const int64_t *)nullptr, (int32_t *)nullptr);
-  HIP_TRY(hipGetLastError());
-  return ARMENV_OK;
-}
-
-int armenv_write_episodes(int32_t device, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap, const uint8_t *done_dev,
-                          int32_t starts_at_reset, const int32_t *counts_dev, const int64_t *offsets_dev,
-                          int32_t *episodes_dev, void *stream) {
-  DEV_ENTER(device);
-  if (T < 0 || N < 1 || ring_cap < T || ring_cap < 1 || ring_base < 0 || !done_dev || !counts_dev || !offsets_dev || !episodes_dev)
-    return fail(ARMENV_EINVAL, "armenv_write_episodes: bad arguments");
-  hipLaunchKernelGGL(index_episodes_kernel, dim3(grid_for(N, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), T, N,
-                     ring_base, ring_cap, done_dev, starts_at_reset, const_cast<int32_t *>(counts_dev), offsets_dev, episodes_dev);
-  HIP_TRY(hipGetLastError());
-  return ARMENV_OK;
-}
-
 int armenv_probe_issue_rate(int32_t device, int32_t precision, int32_t waves_per_simd, double *ns_per_instruction) {
   DEV_ENTER(device);
   if (!ns_per_instruction || waves_per_simd < 1 || waves_per_simd > 8 || (precision != 32 && precision != 64))
@@ -640,18 +617,74 @@ static HerArgs her_args(const ArmEnvHerArgs *a) {
 
 extern "C" {
 
-int armenv_her_sample(int32_t device, const ArmEnvHerArgs *a, void *stream) {
+// ---- the trajectory store.  All six entry points refuse a bad argument by its name before the first HIP call, return ARMENV_OK
+// without a launch for an empty batch, then launch their own kernel form.  One set of checks: the single forms are members = 1.
+#define STORE_REFUSE(why) \
+  if (const char *why_ = (why)) return fail(ARMENV_EINVAL, "%s: %s", __func__, why_)
+
+// what is wrong with the geometry of an index pass and the pointers it reads: the first broken field, or nullptr.  The count pass
+// reads neither offsets_dev nor episodes_dev (write = false).
+static const char *index_refusal(int32_t members, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap, const void *done_dev,
+                                 const void *counts_dev, bool write = false, const void *offsets_dev = nullptr,
+                                 const void *episodes_dev = nullptr, int64_t episodes_stride = 1) {
+  if (members < 1 || members > 64) return "members must be 1..64";
+  if (T < 0) return "T must be >= 0";
+  if (N < 1) return "N must be >= 1";
+  if (ring_cap < 1 || ring_cap < T) return "ring_cap must be >= max(T, 1)";
+  if (ring_base < 0) return "ring_base must be >= 0";
+  if (!done_dev) return "done_dev is NULL";
+  if (!counts_dev) return "counts_dev is NULL";
+  if (write && !offsets_dev) return "offsets_dev is NULL";
+  if (write && !episodes_dev) return "episodes_dev is NULL";
+  if (write && episodes_stride < 1) return "episodes_stride must be >= 1";
+  return nullptr;
+}
+
+// the same for the arguments of a sample; `pop`: the population struct around `a`, or nullptr
+static const char *her_refusal(const ArmEnvHerArgs *a, const ArmEnvHerPopArgs *pop = nullptr) {
+  if (!a) return "args is NULL";
+  if (pop && (pop->members < 1 || pop->members > 64)) return "members must be 1..64";
+  if (pop && pop->episodes_stride < 1) return "episodes_stride must be >= 1";
+  if (a->obs_dim != 6 && a->obs_dim != 9) return "obs_dim must be 6 or 9";
+  if (a->batch < 0) return "batch must be >= 0";
+  if (a->T < 1) return "T must be >= 1";
+  if (a->N < 1) return "N must be >= 1";
+  if (a->ring_cap < a->T) return "ring_cap must be >= T";
+  if (a->ring_base < 0) return "ring_base must be >= 0";
+#define NEEDS(field) if (!a->field) return #field " is NULL"
+  NEEDS(obs0_dev); NEEDS(obs_after_dev); NEEDS(next_obs_dev); NEEDS(action_dev); NEEDS(reward_dev); NEEDS(done_dev);
+  NEEDS(episodes_dev); NEEDS(num_episodes_dev); NEEDS(states_dev); NEEDS(actions_dev); NEEDS(next_states_dev); NEEDS(rewards_dev);
+  NEEDS(dones_dev);
+#undef NEEDS
+  if (!(a->her_ratio >= 0.f && a->her_ratio <= 1.f)) return "her_ratio outside [0,1]";
+  return nullptr;
+}
+
+int armenv_count_episodes(int32_t device, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap, const uint8_t *done_dev,
+                          int32_t starts_at_reset, int32_t *counts_dev, void *stream) {
+  STORE_REFUSE(index_refusal(1, T, N, ring_base, ring_cap, done_dev, counts_dev));
   DEV_ENTER(device);
-  if (!a) return fail(ARMENV_EINVAL, "armenv_her_sample: args is NULL");
-  if (a->obs_dim != 6 && a->obs_dim != 9) return fail(ARMENV_EINVAL, "armenv_her_sample: obs_dim must be 6 or 9");
-  if (a->batch < 0 || a->T < 1 || a->N < 1 || a->ring_cap < a->T || a->ring_base < 0)
-    return fail(ARMENV_EINVAL, "armenv_her_sample: bad sizes");
-  if (!a->obs0_dev || !a->obs_after_dev || !a->next_obs_dev || !a->action_dev || !a->reward_dev || !a->done_dev ||
-      !a->episodes_dev || !a->num_episodes_dev || !a->states_dev || !a->actions_dev || !a->next_states_dev ||
-      !a->rewards_dev || !a->dones_dev)
-    return fail(ARMENV_EINVAL, "armenv_her_sample: NULL buffer");
-  if (!(a->her_ratio >= 0.f && a->her_ratio <= 1.f)) return fail(ARMENV_EINVAL, "armenv_her_sample: her_ratio outside [0,1]");
+  hipLaunchKernelGGL(index_episodes_kernel, dim3(grid_for(N, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), T, N,
+                     ring_base, ring_cap, done_dev, starts_at_reset, counts_dev, (const int64_t *)nullptr, (int32_t *)nullptr);
+  HIP_TRY(hipGetLastError());
+  return ARMENV_OK;
+}
+
+int armenv_write_episodes(int32_t device, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap, const uint8_t *done_dev,
+                          int32_t starts_at_reset, const int32_t *counts_dev, const int64_t *offsets_dev,
+                          int32_t *episodes_dev, void *stream) {
+  STORE_REFUSE(index_refusal(1, T, N, ring_base, ring_cap, done_dev, counts_dev, true, offsets_dev, episodes_dev));
+  DEV_ENTER(device);
+  hipLaunchKernelGGL(index_episodes_kernel, dim3(grid_for(N, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), T, N,
+                     ring_base, ring_cap, done_dev, starts_at_reset, const_cast<int32_t *>(counts_dev), offsets_dev, episodes_dev);
+  HIP_TRY(hipGetLastError());
+  return ARMENV_OK;
+}
+
+int armenv_her_sample(int32_t device, const ArmEnvHerArgs *a, void *stream) {
+  STORE_REFUSE(her_refusal(a));
   if (a->batch == 0) return ARMENV_OK;
+  DEV_ENTER(device);
   const HerArgs h = her_args(a);
   const dim3 grid(grid_for(a->batch, 256)), block(256);
   if (a->obs_dim == 6) hipLaunchKernelGGL((her_sample_kernel<6>), grid, block, 0, static_cast<hipStream_t>(stream), h);
@@ -660,25 +693,9 @@ int armenv_her_sample(int32_t device, const ArmEnvHerArgs *a, void *stream) {
   return ARMENV_OK;
 }
 
-// ---- the population forms: every argument is checked before the first HIP call
-#define POP_REFUSE(cond, what) \
-  if (cond) return fail(ARMENV_EINVAL, "%s: %s", __func__, what)
-
-static const char *pop_index_refusal(int32_t members, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap) {
-  if (members < 1 || members > 64) return "members must be 1..64";
-  if (T < 0) return "T must be >= 0";
-  if (N < 1) return "N must be >= 1";
-  if (ring_cap < 1 || ring_cap < T) return "ring_cap must be >= max(T, 1)";
-  if (ring_base < 0) return "ring_base must be >= 0";
-  return nullptr;
-}
-
 int armenv_pop_count_episodes(int32_t device, int32_t members, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap,
                               const uint8_t *done_dev, int32_t starts_at_reset, int32_t *counts_dev, void *stream) {
-  const char *why = pop_index_refusal(members, T, N, ring_base, ring_cap);
-  POP_REFUSE(why, why);
-  POP_REFUSE(!done_dev, "done_dev is NULL");
-  POP_REFUSE(!counts_dev, "counts_dev is NULL");
+  STORE_REFUSE(index_refusal(members, T, N, ring_base, ring_cap, done_dev, counts_dev));
   DEV_ENTER(device);
   hipLaunchKernelGGL(index_episodes_pop_kernel, dim3(grid_for(N, 256), members), dim3(256), 0, static_cast<hipStream_t>(stream), T, N,
                      ring_base, ring_cap, done_dev, starts_at_reset, counts_dev, (const int64_t *)nullptr, (int32_t *)nullptr,
@@ -690,13 +707,7 @@ int armenv_pop_count_episodes(int32_t device, int32_t members, int64_t T, int64_
 int armenv_pop_write_episodes(int32_t device, int32_t members, int64_t T, int64_t N, int64_t ring_base, int64_t ring_cap,
                               const uint8_t *done_dev, int32_t starts_at_reset, const int32_t *counts_dev,
                               const int64_t *offsets_dev, int32_t *episodes_dev, int64_t episodes_stride, void *stream) {
-  const char *why = pop_index_refusal(members, T, N, ring_base, ring_cap);
-  POP_REFUSE(why, why);
-  POP_REFUSE(!done_dev, "done_dev is NULL");
-  POP_REFUSE(!counts_dev, "counts_dev is NULL");
-  POP_REFUSE(!offsets_dev, "offsets_dev is NULL");
-  POP_REFUSE(!episodes_dev, "episodes_dev is NULL");
-  POP_REFUSE(episodes_stride < 1, "episodes_stride must be >= 1");
+  STORE_REFUSE(index_refusal(members, T, N, ring_base, ring_cap, done_dev, counts_dev, true, offsets_dev, episodes_dev, episodes_stride));
   DEV_ENTER(device);
   hipLaunchKernelGGL(index_episodes_pop_kernel, dim3(grid_for(N, 256), members), dim3(256), 0, static_cast<hipStream_t>(stream), T, N,
                      ring_base, ring_cap, done_dev, starts_at_reset, const_cast<int32_t *>(counts_dev), offsets_dev, episodes_dev,
@@ -706,22 +717,8 @@ int armenv_pop_write_episodes(int32_t device, int32_t members, int64_t T, int64_
 }
 
 int armenv_her_pop_sample(int32_t device, const ArmEnvHerPopArgs *args, void *stream) {
-  POP_REFUSE(!args, "args is NULL");
+  STORE_REFUSE(her_refusal(args ? &args->one : nullptr, args));
   const ArmEnvHerArgs *a = &args->one;
-  POP_REFUSE(args->members < 1 || args->members > 64, "members must be 1..64");
-  POP_REFUSE(args->episodes_stride < 1, "episodes_stride must be >= 1");
-  POP_REFUSE(a->obs_dim != 6 && a->obs_dim != 9, "obs_dim must be 6 or 9");
-  POP_REFUSE(a->batch < 0, "batch must be >= 0");
-  POP_REFUSE(a->T < 1, "T must be >= 1");
-  POP_REFUSE(a->N < 1, "N must be >= 1");
-  POP_REFUSE(a->ring_cap < a->T, "ring_cap must be >= T");
-  POP_REFUSE(a->ring_base < 0, "ring_base must be >= 0");
-#define POP_NEEDS(field) POP_REFUSE(!a->field, #field " is NULL")
-  POP_NEEDS(obs0_dev); POP_NEEDS(obs_after_dev); POP_NEEDS(next_obs_dev); POP_NEEDS(action_dev); POP_NEEDS(reward_dev);
-  POP_NEEDS(done_dev); POP_NEEDS(episodes_dev); POP_NEEDS(num_episodes_dev); POP_NEEDS(states_dev); POP_NEEDS(actions_dev);
-  POP_NEEDS(next_states_dev); POP_NEEDS(rewards_dev); POP_NEEDS(dones_dev);
-#undef POP_NEEDS
-  POP_REFUSE(!(a->her_ratio >= 0.f && a->her_ratio <= 1.f), "her_ratio outside [0,1]");
   if (a->batch == 0) return ARMENV_OK;
   DEV_ENTER(device);
   const HerArgs h = her_args(a);
@@ -733,7 +730,7 @@ int armenv_her_pop_sample(int32_t device, const ArmEnvHerPopArgs *args, void *st
   HIP_TRY(hipGetLastError());
   return ARMENV_OK;
 }
-#undef POP_REFUSE
+#undef STORE_REFUSE
 
 int64_t armenv_num_envs(const ArmEnv *env) { return env ? env->cfg.num_envs : 0; }
 int32_t armenv_obs_dim(const ArmEnv *env) { return env ? (env->cfg.task == ARMENV_TASK_REACH ? 6 : 9) : 0; }

@@ -453,7 +453,8 @@ int armenv_her_sample(int32_t device, const ArmEnvHerArgs *args, void *stream);
  *   obs0 [P][N][D];  obs_after, next_obs [P][ring_cap][N][D];  action [P][ring_cap][N][3];  reward, done [P][ring_cap][N];
  *   episodes i32 [P][episodes_stride][3];  num_episodes i64 [P];  counts i32 [P][N];  offsets i64 [P][N]
  *   outputs [P][B][D], [P][B][3], [P][B];  picks in and out [P][B][4].
- * All three refuse a bad argument with ARMENV_EINVAL, the field named in armenv_last_error(), before any HIP call. */
+ * All three, and the three single forms above (armenv_count_episodes, armenv_write_episodes, armenv_her_sample: the same checks
+ * with members = 1), refuse a bad argument with ARMENV_EINVAL, the field named in armenv_last_error(), before any HIP call. */
 
 /* armenv_count_episodes / armenv_write_episodes for every member at once: one thread per (member, env column).
  * offsets_dev = the inclusive cumsum of counts_dev WITHIN each member (torch.cumsum(counts, 1)); member p's list, E_p =

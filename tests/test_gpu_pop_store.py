@@ -306,3 +306,45 @@ def test_the_loop_trains_the_same_bits_with_either_store(algo):
     for name in a.stacks:
         for x, y in zip(a.stacks[name], b.stacks[name]):
             assert torch.equal(x, y), name
+
+
+# ------------------------------------------------------------------------------------------------ C8
+
+@pytest.mark.parametrize("D", [6, 9])
+def test_the_single_store_hands_the_single_entry_point_its_arguments(D):
+    """armenv_her_sample called through ctypes with an ArmEnvHerArgs filled here by hand, against TrajectoryStore.sample over the same
+    ring (N = 3, cap 40, a wrapped window of 23 steps that starts mid-episode): the same bytes.  The store's second draw goes into the
+    first one's `out`, so it runs on the kept argument struct and writes `picks` in place."""
+    import ctypes as C
+
+    from armenv import _lib as L
+    from armenv.replay import TrajectoryStore
+    st, linear = _store(1, 3, D, 23, 31, 0)
+    assert len(_complete_episodes(linear[0], 0)) >= 2                 # the shared inputs' precondition
+    view = st.member_view(0)
+    lib, stream = L.load(), C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
+    for B in (1, 257):
+        for use_her in (True, False):
+            single = TrajectoryStore(device=DEV, seed=SEED)
+            single.chunk = view
+            got = None
+            for d in (0, 1):
+                ref = dict(states=torch.full((B, D), 3.0, device=DEV), actions=torch.full((B, 3), 3.0, device=DEV),
+                           next_states=torch.full((B, D), 3.0, device=DEV), rewards=torch.full((B,), 3.0, device=DEV),
+                           dones=torch.full((B,), 3, dtype=torch.uint8, device=DEV),
+                           picks=torch.full((B, 4), 3, dtype=torch.int32, device=DEV))
+                a = L.ArmEnvHerArgs()
+                a.T, a.N, a.ring_base, a.ring_cap, a.obs_dim, a.use_her = 23, 3, 31, CAP, D, int(use_her)
+                a.obs0_dev, a.obs_after_dev, a.next_obs_dev = view["obs0"].data_ptr(), view["obs_after"].data_ptr(), view["next_obs"].data_ptr()
+                a.action_dev, a.reward_dev, a.done_dev = view["action"].data_ptr(), view["reward"].data_ptr(), view["done"].data_ptr()
+                a.episodes_dev, a.num_episodes_dev = view["episodes"].data_ptr(), view["num_episodes"].data_ptr()
+                a.batch, a.picks_dev, a.seed, a.draw, a.her_ratio, a.dis_threshold = B, None, SEED, d, 0.8, 0.1
+                a.states_dev, a.actions_dev, a.next_states_dev = ref["states"].data_ptr(), ref["actions"].data_ptr(), ref["next_states"].data_ptr()
+                a.rewards_dev, a.dones_dev, a.picks_out_dev = ref["rewards"].data_ptr(), ref["dones"].data_ptr(), ref["picks"].data_ptr()
+                L.check(lib.armenv_her_sample(0, C.byref(a), stream))
+                single._draw = d
+                picks = None if got is None else got["picks"].data_ptr()
+                got = single.sample(B, use_her=use_her, her_ratio=0.8, return_picks=True, out=got)
+                assert single._draw == d + 1 and picks in (None, got["picks"].data_ptr())
+                for k in BATCH + ("picks",):
+                    assert torch.equal(got[k], ref[k]), (B, use_her, d, k)

@@ -1,7 +1,8 @@
 """CPU tests of the host side of the population trajectory store (armenv_her_pop_sample, armenv_pop_count_episodes,
 armenv_pop_write_episodes, include/armenv.h; armenv.replay.PopulationTrajectoryStore): the ctypes struct agrees with the header, every
-argument is refused before any HIP call, the population kernels are in the built code object without scratch or LDS, and the stacked
-rings keep TrajectoryStore's books."""
+argument is refused before any HIP call -- by the single entry points too, which run the same checks --, the population kernels are
+in the built code object without scratch or LDS, the stacked rings keep TrajectoryStore's books, and both stores' host side
+(armenv.replay._Store) keeps its contracts on device="cpu"."""
 import ctypes as C
 
 import pytest
@@ -117,6 +118,38 @@ def test_bad_write_arguments_are_refused_before_any_device_call(field, change):
                              g["counts"], g["offsets"], g["episodes"], g["stride"], None)
 
 
+# The single entry points run the same checks with members = 1: the tables above without their `members` / `episodes_stride` rows.
+SINGLE_SAMPLE_REFUSALS = [row for row in SAMPLE_REFUSALS if row[0] not in ("members", "episodes_stride")]
+SINGLE_INDEX_REFUSALS = [row for row in INDEX_REFUSALS if row[0] != "members"]
+
+
+@pytest.mark.parametrize("field,mutate", SINGLE_SAMPLE_REFUSALS)
+def test_the_single_sample_refuses_the_same_fields_before_any_device_call(field, mutate):
+    pa = _args()
+    mutate(pa)
+    assert field in _refused("armenv_her_sample", 0, C.byref(pa.one), None)
+
+
+def test_the_single_sample_refuses_null_args_and_accepts_an_empty_batch():
+    from armenv import _lib as L
+    assert "args" in _refused("armenv_her_sample", 0, None, None)
+    pa = _args(B=0)
+    assert L.load().armenv_her_sample(0, C.byref(pa.one), None) == 0
+
+
+@pytest.mark.parametrize("field,change", SINGLE_INDEX_REFUSALS)
+def test_the_single_count_refuses_the_same_fields_before_any_device_call(field, change):
+    g = dict(GOOD_INDEX, **change)
+    assert field in _refused("armenv_count_episodes", 0, g["T"], g["N"], g["ring_base"], g["ring_cap"], g["done"], 1, g["counts"], None)
+
+
+@pytest.mark.parametrize("field,change", SINGLE_INDEX_REFUSALS + [("offsets_dev", dict(offsets=None)), ("episodes_dev", dict(episodes=None))])
+def test_the_single_write_refuses_the_same_fields_before_any_device_call(field, change):
+    g = dict(GOOD_INDEX, **change)
+    assert field in _refused("armenv_write_episodes", 0, g["T"], g["N"], g["ring_base"], g["ring_cap"], g["done"], 1, g["counts"],
+                             g["offsets"], g["episodes"], None)
+
+
 # ------------------------------------------------------------------------------------------------ H3: kernels present
 
 @pytest.fixture(scope="module")
@@ -180,6 +213,94 @@ def test_population_rings_keep_the_single_stores_books(monkeypatch):
             assert torch.equal(view["obs0"], s._ring["obs0"])
         seen.append((r["base"], r["T"], r["at_reset"]))
     assert seen == [(0, 25, True), (0, 50, True), (0, 75, True), (20, 80, False), (45, 80, False), (70, 80, False)]
+
+
+# ------------------------------------------------------------------------------------------------ H5: one code path
+
+@pytest.fixture
+def unindexed(monkeypatch):
+    """armenv.replay with the index launches left out, so that the stores' host side runs on the cpu device"""
+    from armenv import replay
+    monkeypatch.setattr(replay.TrajectoryStore, "_index", lambda self: None)
+    monkeypatch.setattr(replay.PopulationTrajectoryStore, "_index", lambda self: None)
+    return replay
+
+
+def _rollout(gen, lead, Tc, N, D):
+    f = lambda *shape: torch.rand(lead + shape, generator=gen)
+    return dict(obs=f(Tc, N, D), terminal_obs=f(Tc, N, D), actions=f(Tc, N, 3), reward=f(Tc, N), done_u8=(f(Tc, N) < 0.3).to(torch.uint8))
+
+
+def test_a_store_without_capacity_holds_the_rollouts_own_tensors(unindexed):
+    Tc, N, D = 7, 3, 6
+    gen = torch.Generator().manual_seed(4)
+    out, obs0 = _rollout(gen, (), Tc, N, D), torch.rand(N, D, generator=gen)
+    st = unindexed.TrajectoryStore(device="cpu")
+    assert st.chunk is None and st.capacity is None
+    st.add_rollout(obs0, out, starts_at_reset=False)
+    ch = st.chunk
+    assert (ch["cap"], ch["base"], ch["T"]) == (Tc, 0, Tc) and (ch["N"], ch["D"], ch["at_reset"]) == (N, D, False)
+    for ring, src in (("obs_after", "obs"), ("next_obs", "terminal_obs"), ("action", "actions"), ("reward", "reward"), ("done", "done_u8")):
+        assert ch[ring].data_ptr() == out[src].data_ptr(), ring
+    assert ch["obs0"].data_ptr() == obs0.data_ptr()
+
+
+def test_host_trajectories_join_the_ring_with_their_own_first_state(unindexed):
+    """Episodes of 3 and 2 steps: the second one's first state stands where the sampler looks for it, in obs_after at the first
+    episode's last row, and that row's next_obs -- the first episode's own last state -- is not touched."""
+    D = 6
+    gen = torch.Generator().manual_seed(5)
+    episodes = []
+    for length in (3, 2):
+        states = torch.rand(length + 1, D, generator=gen)
+        traj = unindexed.Trajectory(states[0].numpy())
+        for t in range(length):
+            traj.store_step(torch.rand(3, generator=gen).numpy(), states[t + 1].numpy(), -0.1 * (t + 1), t == length - 1)
+        episodes.append((traj, states))
+    st = unindexed.TrajectoryStore(device="cpu", capacity_steps=8)
+    st.add_trajectory(episodes[0][0])
+    r = st.chunk
+    assert (r["T"], r["at_reset"]) == (3, True) and torch.equal(r["obs_after"][:3, 0], episodes[0][1][1:])
+    st.add_trajectory(episodes[1][0])
+    assert st.chunk is r and (r["cap"], r["base"], r["T"], r["N"], r["at_reset"]) == (8, 0, 5, 1, True)
+    assert torch.equal(r["obs_after"][2, 0], episodes[1][1][0])                # the second episode's first state
+    assert torch.equal(r["next_obs"][2, 0], episodes[0][1][3])                 # the first episode's last state
+    assert torch.equal(r["obs_after"][3:5, 0], episodes[1][1][1:]) and torch.equal(r["next_obs"][3:5, 0], episodes[1][1][1:])
+    assert torch.equal(r["obs0"][0], episodes[0][1][0])
+    assert r["done"][:5, 0].tolist() == [0, 0, 1, 0, 1] and torch.equal(r["reward"][:5, 0], torch.tensor([-0.1, -0.2, -0.3, -0.1, -0.2]))
+
+
+@pytest.mark.parametrize("population", [False, True])
+def test_sample_refuses_a_missing_rollout_and_unfit_out_tensors(unindexed, population):
+    import re
+    B, N, D, Tc = 4, 2, 6, 5
+    gen = torch.Generator().manual_seed(6)
+    if population:
+        st, lead = unindexed.PopulationTrajectoryStore(3, device="cpu", capacity_steps=8), (3,)
+    else:
+        st, lead = unindexed.TrajectoryStore(device="cpu", capacity_steps=8), ()
+    name = type(st).__name__
+    with pytest.raises(RuntimeError, match=re.escape(name + ".sample: no rollout stored")):
+        st.sample(B)
+    if population:
+        st.rollout_buffers(Tc, N, D)
+        for k, t in _rollout(gen, lead, Tc, N, D).items():
+            st._staging[k].copy_(t)
+        st.add_rollouts(torch.rand(3, N, D, generator=gen))
+    else:
+        st.add_rollout(torch.rand(N, D, generator=gen), _rollout(gen, lead, Tc, N, D))
+    assert st.chunk["T"] == Tc
+    unfit = dict(states=torch.zeros(lead + (B, 2 * D))[..., ::2],              # the right shape, not contiguous
+                 dones=torch.zeros(lead + (B,)),                               # the wrong dtype
+                 rewards=torch.zeros(lead + (B, 1)))                           # the wrong shape
+    assert tuple(unfit["states"].shape) == lead + (B, D) and not unfit["states"].is_contiguous()
+    for key, tensor in unfit.items():
+        out = dict(states=torch.zeros(lead + (B, D)), actions=torch.zeros(lead + (B, 3)), next_states=torch.zeros(lead + (B, D)),
+                   rewards=torch.zeros(lead + (B,)), dones=torch.zeros(lead + (B,), dtype=torch.uint8))
+        out[key] = tensor
+        with pytest.raises(ValueError, match=re.escape(f"{name}.sample: out[{key!r}] must be a contiguous")):
+            st.sample(B, out=out)
+    assert st._draw == 0 and st._bound is None                                 # a refused call draws nothing and binds nothing
 
 
 def test_population_store_refuses_unsupported_construction():
