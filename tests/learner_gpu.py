@@ -1,13 +1,13 @@
 """What the GPU tests of the single fused learners share (test infrastructure): random batches on cuda:0, a learner's tensors by name
-and the gradient rule of tests/test_gpu_*_fused.py; and the bookkeeping of the float64 comparisons of tests/test_gpu_td3_ref64.py and
-tests/test_gpu_da_ref64.py: |got - ref| <= C[kind] 2^-24 M_ref + allowance_ref per element, the largest measured ratios on the side."""
+and the gradient rule of tests/test_gpu_*_fused.py; and the bookkeeping of the float64 comparisons of tests/learner_ref64_gpu.py:
+|got - ref| <= C[kind] 2^-24 M_ref + allowance_ref per element, the largest measured ratios on the side."""
 import copy
 import json
 import os
 
 import torch
 
-import td3_ref64 as R
+import learner_ref64 as R
 
 DEV = "cuda:0"
 

@@ -1,5 +1,5 @@
 """CPU tests of the fused TD3 learner's host side (armenv_td3_update, include/armenv.h ABI 7): the ctypes structs agree with the
-header, every argument is validated before any HIP call, and the learner kernels' code objects hold what DESIGN.md section 4 claims
+header, every argument is validated before any HIP call, the batch-size limits, and the learner kernels' code objects hold what DESIGN.md section 4 claims
 (no scratch, exact-f32 MFMA, no atomics)."""
 import ctypes as C
 
@@ -38,6 +38,22 @@ def test_workspace_size_queries():
     small, big = lib.armenv_td3_workspace_bytes(6, 256, 1000), lib.armenv_td3_workspace_bytes(6, 256, 2048)
     assert 0 < small < big and small % 256 == 0
     assert big >= 16 * 2048 * 256 * 4             # at least the sixteen [B][256] activations and deltas
+
+
+def test_workspace_query_at_the_batch_limit():
+    from armenv import _lib as L
+    lib = L.load()
+    for D in (1, 6, 12):
+        assert lib.armenv_td3_workspace_bytes(D, 256, 2 ** 20) > 0
+        assert lib.armenv_td3_workspace_bytes(D, 256, 2 ** 20 + 1) == -1
+
+
+def test_update_refuses_a_batch_above_the_limit():
+    from armenv import _lib as L
+    lib, a = L.load(), fake_args("td3")
+    a.batch = 2 ** 20 + 1
+    rc, msg = lib.armenv_td3_update(C.byref(a), None), lib.armenv_last_error().decode()
+    assert rc == -1 and "batch" in msg and "armenv_td3_update" in msg, (rc, msg)
 
 
 def test_learner_kernels_are_present_without_scratch(learner_kernels):

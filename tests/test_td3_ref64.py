@@ -1,17 +1,18 @@
-"""CPU tests of tests/td3_ref64.py, the float64 restatement of one TD3 update that the fused HIP update is tested against: it
-reproduces the reference's own golden updates, equals torch autograd in float64, and every defect switch breaks that equality.
-Also: the host restatement of the kernel's target-policy noise, and the batch-size limits of the C ABI."""
-import ctypes as C
-
+"""CPU tests of tests/learner_ref64.py for TD3, the float64 restatement of one update that the fused HIP update is tested against:
+it reproduces the reference's own golden updates, equals torch autograd in float64, every defect switch breaks that equality, and
+every TD3 case of tests/test_gpu_td3_ref64.py (tests/learner_cases.py) keeps its share of ambiguous relu units under the cap (the
+bodies shared with tests/test_da_ref64.py are tests/learner_ref64_checks.py's).  Also: the host restatement of the kernel's
+target-policy noise."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden_npz
-import td3_ref64 as R
+import learner_cases as K
+import learner_ref64 as R
+pytest.register_assert_rewrite("learner_ref64_checks")          # the shared bodies assert there
+import learner_ref64_checks as X  # noqa: E402
 
-HP = dict(action_bound=0.7, gamma=0.98, tau=0.005, policy_noise=0.2, noise_clip=0.5, actor_lr=1e-3, critic_lr=1e-3, beta1=0.9,
-          beta2=0.999, eps=1e-8)
 KEYS = ("states", "actions", "next_states", "rewards", "dones")
 
 
@@ -22,101 +23,33 @@ def test_reference_reproduces_the_golden_updates():
     from armenv.td3 import TD3
     g = golden_npz("td3_train_seed0.npz")
     torch.manual_seed(0)
-    t = TD3(6, 3, 0.7, device="cpu")
-    st = R.state_from(t.actor, t.critic, t.target_actor, t.target_critic, [torch.zeros_like(p) for p in t.actor.parameters()],
-                      [torch.zeros_like(p) for p in t.actor.parameters()], [torch.zeros_like(p) for p in t.critic.parameters()],
-                      [torch.zeros_like(p) for p in t.critic.parameters()], 0, 0)
+    st = X.zeros("td3", TD3(6, 3, 0.7, device="cpu"))
     torch.manual_seed(123)
     for i, want in enumerate(g["losses"]):
         b = {k: torch.from_numpy(g[f"b{i}_{k}"]).to(torch.float64) for k in KEYS}
         noise = torch.randn(64, 3).to(torch.float64)
-        with_actor = (i + 1) % 3 == 0
-        out = R.td3_update(st, b, noise, HP, with_actor)
+        out = R.update("td3", st, b, noise, X.HP_GOLDEN, with_actor=(i + 1) % 3 == 0)
         assert abs(out["loss"] - want) < 1e-5 * max(1.0, abs(want)), (i, out["loss"], want)
-        st = R.advance(st, out, with_actor)
+        st = R.advance(st, out)
     assert st["critic_step"] == 6 and st["actor_step"] == 2
-    for name, net in (("actor", t.actor), ("critic", t.critic), ("target_actor", t.target_actor), ("target_critic", t.target_critic)):
-        for (k, _), v in zip(net.state_dict().items(), st[name]):
-            ref = g[f"{name}__{k.replace('.', '_')}"]
-            assert np.abs(v.numpy() - ref).max() < 1e-5, (name, k, np.abs(v.numpy() - ref).max())
-
-
-def _torch_state(t):
-    (am, av, a_step), (cm, cv, c_step) = R.adam_state(t.actor, t.actor_opt), R.adam_state(t.critic, t.critic_opt)
-    return R.state_from(t.actor, t.critic, t.target_actor, t.target_critic, am, av, cm, cv, a_step, c_step)
-
-
-def _autograd_case(B, D, with_actor, seed, monkeypatch, hp, target_actor_gain=1.0):
-    """armenv.td3.TD3's networks and Adam in float64 (torch autograd), two priming updates, then one more with or without the actor
-    step.  Returns (state before it, batch, noise, the torch learner after it, its critic loss).  target_actor_gain scales the
-    target actor's last layer (pre-tanh outputs of order one, so that target actions reach the clamp)."""
-    from armenv.td3 import TD3
-    torch.manual_seed(seed)
-    t = TD3(D, 3, hp["action_bound"], device="cpu", actor_lr=hp["actor_lr"], critic_lr=hp["critic_lr"], tau=hp["tau"],
-            gamma=hp["gamma"], policy_noise=hp["policy_noise"], noise_clip=hp["noise_clip"], policy_freq=1)
-    for n in t._nets():
-        n.double()
-    with torch.no_grad():
-        t.target_actor.fc3.weight.mul_(target_actor_gain)
-    gen = torch.Generator().manual_seed(seed + 1)
-
-    def update(batch, noise, flag):
-        monkeypatch.setattr(torch, "randn_like", lambda x: noise.clone())
-        try:
-            return t._update(batch["states"], batch["actions"], batch["rewards"].view(-1, 1), batch["next_states"],
-                             batch["dones"].view(-1, 1), flag)
-        finally:
-            monkeypatch.undo()
-    for _ in range(2):
-        update(R.random_batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64), True)
-    st = _torch_state(t)
-    batch, noise = R.random_batch(gen, B, D), torch.randn(B, 3, generator=gen, dtype=torch.float64)
-    loss = float(update(batch, noise, with_actor))
-    return st, batch, noise, t, loss
-
-
-def _autograd_failures(out, t, loss, with_actor, tol=2.0 ** -18):
-    """names of the quantities of `out` that differ from the float64 autograd learner `t` by more than tol 2^-24 (= 2^-42, a few
-    hundred float64 roundings) times their magnitude, plus the allowance"""
-    bad = []
-    if abs(out["loss"] - loss) > tol * R.U * out["loss_mag"]:
-        bad.append("loss")
-    sides = [("critic", t.critic, t.target_critic)] + ([("actor", t.actor, t.target_actor)] if with_actor else [])
-    for name, net, tnet in sides:
-        for k, p in enumerate(net.parameters()):
-            if R.bad_elements(p.grad.detach(), out[name + "_grad"][k], out[name + "_grad_mag"][k], out[name + "_grad_allow"][k], tol)[0]:
-                bad.append(f"{name}_grad{k}")
-            if R.bad_elements(p.detach(), out[name][k], out[name + "_mag"][k], 0 * p, tol)[0]:
-                bad.append(f"{name}{k}")
-        if with_actor:
-            for k, p in enumerate(tnet.parameters()):
-                if R.bad_elements(p.detach(), out["target_" + name][k], out["target_" + name + "_mag"][k], 0 * p, tol)[0]:
-                    bad.append(f"target_{name}{k}")
-    return bad
+    X.assert_golden_nets("td3", st, g)
 
 
 @pytest.mark.parametrize("with_actor", [False, True])
 @pytest.mark.parametrize("B,D,seed", [(65, 6, 0), (300, 9, 1), (7, 1, 2), (257, 12, 3)])
-def test_reference_equals_autograd_in_float64(B, D, seed, with_actor, monkeypatch):
-    """Gradients, loss, Adam-stepped parameters and soft-updated targets equal those of armenv.td3.TD3's update run in float64 with
-    torch autograd and torch.optim.Adam, from primed (non-zero) Adam moments, to 2^-42 of their magnitudes."""
-    st, batch, noise, t, loss = _autograd_case(B, D, with_actor, seed, monkeypatch, HP)
-    out = R.td3_update(st, batch, noise, HP, with_actor, chunk=64)           # several chunks
-    assert _autograd_failures(out, t, loss, with_actor) == []
-    assert out["ambiguous"] < 1e-3 * out["units"] and out["units"] == B * 256 * (10 + (4 if with_actor else 0))
+def test_reference_equals_autograd_in_float64(B, D, seed, with_actor):
+    """armenv.td3.TD3's update in float64, with and without the actor step; the reference evaluates B * 256 * (10 + 4) relu units"""
+    X.check_reference_equals_autograd("td3", B, D, None, seed, with_actor)
 
 
-# hyper-parameters under which every defect has something to change: the noise clip binds on many elements, and with target
-# actions of order one (target_actor_gain) the action clamp binds on many others, with and without the clip
-HP_DEFECT = dict(HP, action_bound=0.25, policy_noise=0.4, noise_clip=0.1)
+@pytest.mark.parametrize("defect", R.DEFECTS["td3"])
+def test_every_defect_switch_breaks_the_autograd_comparison(defect):
+    X.check_defect_switch("td3", defect)
 
 
-@pytest.mark.parametrize("defect", R.DEFECTS)
-def test_every_defect_switch_breaks_the_autograd_comparison(defect, monkeypatch):
-    st, batch, noise, t, loss = _autograd_case(300, 6, True, 4, monkeypatch, HP_DEFECT, target_actor_gain=30.0)
-    assert _autograd_failures(R.td3_update(st, batch, noise, HP_DEFECT, True), t, loss, True) == []
-    bad = _autograd_failures(R.td3_update(st, batch, noise, HP_DEFECT, True, defect=defect), t, loss, True)
-    assert bad, defect
+@pytest.mark.parametrize("c", [c for c in K.ALL_CASES if c["agent"] == "td3"], ids=K.case_id)
+def test_gpu_case_inputs_keep_ambiguity_rare(c):
+    X.check_case_inputs(c)
 
 
 # ---- the host restatement of the kernel's noise ----
@@ -177,22 +110,3 @@ def test_kernel_noise_streams_differ():
         assert not np.any(other == base), (seed, draw)
     z = R.kernel_noise(0, 1, np.arange(1000))
     assert len(np.unique(z)) == z.size
-
-
-# ---- batch-size limits of the C ABI ----
-
-def test_workspace_query_at_the_batch_limit():
-    from armenv import _lib as L
-    lib = L.load()
-    for D in (1, 6, 12):
-        assert lib.armenv_td3_workspace_bytes(D, 256, 2 ** 20) > 0
-        assert lib.armenv_td3_workspace_bytes(D, 256, 2 ** 20 + 1) == -1
-
-
-def test_update_refuses_a_batch_above_the_limit():
-    from armenv import _lib as L
-    from learner_host import fake_args
-    lib, a = L.load(), fake_args("td3")
-    a.batch = 2 ** 20 + 1
-    rc, msg = lib.armenv_td3_update(C.byref(a), None), lib.armenv_last_error().decode()
-    assert rc == -1 and "batch" in msg and "armenv_td3_update" in msg, (rc, msg)
