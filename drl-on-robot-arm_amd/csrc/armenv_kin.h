@@ -333,9 +333,36 @@ AE_DEV T fast_rsqrt(T x) {
   return r;
 }
 
+// ARMENV_UNIFORM_ORIENT (the UNI template parameter below): wave-uniform dispatch in front of the select forms of quat_from_frame and
+// acos_branchfree.  The selects pay for every candidate on every trip; where all ACTIVE lanes of the wave agree on a predicate, one
+// ballot and one scalar branch (which falls through on the common side) lead to straight-line code that computes the chosen
+// candidates only, and the select form stays behind as the out-of-line side for waves whose lanes disagree.  A lane evaluates the
+// same expressions either way (qf_* / acos_* below are the one source of each), so the bits do not depend on the side taken, on
+// the other lanes of the wave, or on this switch.  What the reach / push workloads agree on (host replay of the default
+// config: target orientation gripper down, rotation pi): trace < 0 and m22 the smallest diagonal element in every lane, |w| within
+// 1e-6 of 1 (the outer acos form) -- but m00 and m11 are both ~0 there and every wave is split about evenly between the y and the x
+// case, and about half the lanes take the degenerate axis at the first and third trip.  So the dispatch is on the PAIR of cases
+// (x or y, one select left), and orientation_error keeps its clamp and axis selects.
+// Set per kernel family by the callers: on in the peeled trips of the rollout kernels (ik_lockstep) and in ik_move (armenv_ik),
+// off in the trip loops of the step kernel, the fused-actor rollouts and the lane-asynchronous kernel (smaller code).
+#ifndef ARMENV_UNIFORM_ORIENT
+#define ARMENV_UNIFORM_ORIENT 1
+#endif
+AE_DEV bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(!p) == 0ull; }     // p holds in every active lane
+
+// the expressions of btMatrix3x3::getRotation's four cases, one source for the select form and the wave-uniform forms
+template <typename T> AE_DEV T qf_tw(T trace) { return trace + T(1); }
+template <typename T> AE_DEV T qf_tz(T m00, T m11, T m22) { return m22 - m00 - m11 + T(1); }
+template <typename T> AE_DEV T qf_ty(T m00, T m11, T m22) { return m11 - m22 - m00 + T(1); }
+template <typename T> AE_DEV T qf_tx(T m00, T m11, T m22) { return m00 - m11 - m22 + T(1); }
+template <typename T> AE_DEV T qf_half_rsqrt(T t) { return T(0.5) * fast_rsqrt<T>(t); }   // 0.5 / sqrt(t)
+template <typename T> AE_DEV T qf_big(T t, T h) { return t * h; }                          // sqrt(t) * 0.5
+template <typename T> AE_DEV T qf_diff(T a, T b, T h) { return (a - b) * h; }
+template <typename T> AE_DEV T qf_sum(T a, T b, T h) { return (a + b) * h; }
+
 // btMatrix3x3::getRotation (Bullet src/LinearMath/btMatrix3x3.h): rotation matrix -> quaternion xyzw.
 // m(r,c) = W[3*c + r].
-template <typename T>
+template <typename T, int UNI = 0>
 AE_DEV void quat_from_frame(const T (&W)[9], T (&q)[4]) {
   const T m00 = W[0], m10 = W[1], m20 = W[2], m01 = W[3], m11 = W[4], m21 = W[5], m02 = W[6], m12 = W[7], m22 = W[8];
   // Same case selection as getRotation (trace > 0, else the largest diagonal element), evaluated with selects
@@ -347,17 +374,42 @@ AE_DEV void quat_from_frame(const T (&W)[9], T (&q)[4]) {
   const bool cz = !cw & (m00 < m11 ? (m11 < m22) : (m00 < m22));
   const bool cy = !cw & !cz & (m00 < m11);
   // cx otherwise
-  const T tw = trace + T(1), tz = m22 - m00 - m11 + T(1), ty = m11 - m22 - m00 + T(1), tx = m00 - m11 - m22 + T(1);
-  const T t = cw ? tw : (cz ? tz : (cy ? ty : tx));
-  const T h = T(0.5) * fast_rsqrt<T>(t);   // 0.5 / sqrt(t)
-  const T big = t * h;                       // sqrt(t) * 0.5
-  const T d21 = (m21 - m12) * h, d02 = (m02 - m20) * h, d10 = (m10 - m01) * h;
-  T s10 = (m10 + m01) * h, s20 = (m20 + m02) * h, s21 = (m21 + m12) * h;
-  asm("" : "+v"(s10), "+v"(s20), "+v"(s21));   // keep the three sums out of a `!cw` branch the compiler would build for them
-  q[0] = cw ? d21 : (cz ? s20 : (cy ? s10 : big));
-  q[1] = cw ? d02 : (cz ? s21 : (cy ? big : s10));
-  q[2] = cw ? d10 : (cz ? big : (cy ? s21 : s20));
-  q[3] = cw ? big : (cz ? d10 : (cy ? d02 : d21));
+  T o0 = T(0), o1 = T(0), o2 = T(0), o3 = T(0);
+  bool agree = false;
+  if constexpr (UNI != 0) {
+    // the y-or-x pair, straight line: two of the four t, five of the six products, one select per value
+    const T ty = qf_ty<T>(m00, m11, m22), tx = qf_tx<T>(m00, m11, m22);
+    const T t = cy ? ty : tx;
+    const T h = qf_half_rsqrt<T>(t);
+    const T big = qf_big<T>(t, h);
+    const T d21 = qf_diff<T>(m21, m12, h), d02 = qf_diff<T>(m02, m20, h);
+    const T s10 = qf_sum<T>(m10, m01, h), s20 = qf_sum<T>(m20, m02, h), s21 = qf_sum<T>(m21, m12, h);
+    o0 = cy ? s10 : big;
+    o1 = cy ? big : s10;
+    o2 = cy ? s21 : s20;
+    o3 = cy ? d02 : d21;
+    // Written as `if (disagree) { select form }` behind the pair's values, not as if / else: hipcc lowers an if / else inside the
+    // trip's exec-mask region to TWO scalar branches on the common side (the else side sets a flag the then side is entered by),
+    // an if alone to one that falls through.  A wave with a lane in the w or the z case pays for the pair's values as well.
+    // The asm keeps them ahead of the branch (sunk behind it they are an else side again); one exit with the values in locals,
+    // because an early return past stores to q loses the branch's weight and with it the out-of-line placement of the select form.
+    asm("" : "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3));
+    agree = wave_all(!cw & !cz);
+  }
+  if (__builtin_expect(!agree, 0)) {
+    const T tw = qf_tw<T>(trace), tz = qf_tz<T>(m00, m11, m22), ty = qf_ty<T>(m00, m11, m22), tx = qf_tx<T>(m00, m11, m22);
+    const T t = cw ? tw : (cz ? tz : (cy ? ty : tx));
+    const T h = qf_half_rsqrt<T>(t);
+    const T big = qf_big<T>(t, h);
+    const T d21 = qf_diff<T>(m21, m12, h), d02 = qf_diff<T>(m02, m20, h), d10 = qf_diff<T>(m10, m01, h);
+    T s10 = qf_sum<T>(m10, m01, h), s20 = qf_sum<T>(m20, m02, h), s21 = qf_sum<T>(m21, m12, h);
+    asm("" : "+v"(s10), "+v"(s20), "+v"(s21));   // keep the three sums out of a `!cw` branch the compiler would build for them
+    o0 = cw ? d21 : (cz ? s20 : (cy ? s10 : big));
+    o1 = cw ? d02 : (cz ? s21 : (cy ? big : s10));
+    o2 = cw ? d10 : (cz ? big : (cy ? s21 : s20));
+    o3 = cw ? big : (cz ? d10 : (cy ? d02 : d21));
+  }
+  q[0] = o0; q[1] = o1; q[2] = o2; q[3] = o3;
 }
 
 // acos on [-1, 1] without branches: fdlibm's e_acos.c rational approximation R(z) = p(z) / q(z), evaluated ONCE on
@@ -365,13 +417,10 @@ AE_DEV void quat_from_frame(const T (&W)[9], T (&q)[4]) {
 // routine is the same arithmetic behind three divergent regions; inside the IK trip that costs a wave the exec-mask
 // bookkeeping of every region on every trip and keeps the error chain out of the scheduler's reach.  ~1 ulp, and the
 // engine rounds the angle through float anyway (IKParams::angle_f32).
-AE_DEV double acos_branchfree(double x) {
-#ifdef ARMENV_EXACT_ACOS
-  return ::acos(x);
-#endif
-  const double ax = ::fabs(x);
-  const bool small = ax < 0.5;
-  const double z = small ? x * x : ::fma(-0.5, ax, 0.5);
+// the pieces of acos_branchfree, one source for its select form and its wave-uniform forms
+AE_DEV double acos_z_inner(double x) { return x * x; }
+AE_DEV double acos_z_outer(double ax) { return ::fma(-0.5, ax, 0.5); }
+AE_DEV double acos_R(double z) {
   double p = ::fma(3.47933107596021167570e-05, z, 7.91534994289814532176e-04);
   p = ::fma(p, z, -4.00555345006794114027e-02);
   p = ::fma(p, z, 2.01212532134862925881e-01);
@@ -382,19 +431,49 @@ AE_DEV double acos_branchfree(double x) {
   q = ::fma(q, z, 2.02094576023350569471e+00);
   q = ::fma(q, z, -2.40339491173441421878e+00);
   q = ::fma(q, z, 1.0);
-  const double R = p * fast_rcp<double>(q);
-  const double sr = z * fast_rsqrt<double>(small ? 1.0 : (z > 0.0 ? z : 1.0));   // sqrt(z) for the two outer forms
+  return p * fast_rcp<double>(q);
+}
+constexpr double kAcosPio2Lo = 6.12323399573676603587e-17;
+AE_DEV double acos_inner(double x, double R) {                               // |x| < 0.5
+  const double pio2_hi = 1.57079632679489655800e+00;
+  return pio2_hi - (x - ::fma(-x, R, kAcosPio2Lo));
+}
+// rs = 1 / sqrt(z), of any positive number where z is 0 (|x| = 1: s = 0 there)
+AE_DEV double acos_outer(double x, double z, double R, double rs) {
+  const double sr = z * rs;                                                  // sqrt(z)
   const double s = z > 0.0 ? sr : 0.0;
-  const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17;
-  const double inner = pio2_hi - (x - ::fma(-x, R, pio2_lo));              // |x| < 0.5
-  const double w = ::fma(R, s, s);                                          // s + s R
-  const double outer = x < 0.0 ? ::fma(-2.0, w - pio2_lo, 3.14159265358979311600e+00) : 2.0 * w;
-  return small ? inner : outer;
+  const double w = ::fma(R, s, s);                                           // s + s R
+  return x < 0.0 ? ::fma(-2.0, w - kAcosPio2Lo, 3.14159265358979311600e+00) : 2.0 * w;
+}
+template <int UNI = 0>
+AE_DEV double acos_branchfree(double x) {
+#ifdef ARMENV_EXACT_ACOS
+  return ::acos(x);
+#endif
+  const double ax = ::fabs(x);
+  const bool small = ax < 0.5;
+  double r = 0.0;
+  bool agree = false;
+  if constexpr (UNI != 0) {
+    // the outer form alone (near convergence |w| is close to 1), and the select form behind it for a wave with a lane inside
+    // |x| < 0.5 -- an if without an else and one exit, as in quat_from_frame
+    const double z = acos_z_outer(ax);
+    r = acos_outer(x, z, acos_R(z), fast_rsqrt<double>(z > 0.0 ? z : 1.0));
+    asm("" : "+v"(r));
+    agree = wave_all(!small);
+  }
+  if (__builtin_expect(!agree, 0)) {
+    const double z = small ? acos_z_inner(x) : acos_z_outer(ax);
+    const double R = acos_R(z);
+    const double outer = acos_outer(x, z, R, fast_rsqrt<double>(small ? 1.0 : (z > 0.0 ? z : 1.0)));
+    r = small ? acos_inner(x, R) : outer;
+  }
+  return r;
 }
 
 // IKTrajectoryHelper::computeIK orientation part: deltaQ = endQ * startQ^-1, angle = 2 acos(w) wrapped to
 // (-pi, pi], e = angle * normalize(axis)  (axis = (1,0,0) when 1 - w^2 < 10 eps).
-template <typename T>
+template <typename T, int UNI = 0>
 AE_DEV void orientation_error(const T (&tq)[4], const T (&qc)[4], int angle_f32, T (&e)[3]) {
   using M = Mth<T>;
   const T bx = -qc[0], by = -qc[1], bz = -qc[2], bw = qc[3];
@@ -416,7 +495,7 @@ AE_DEV void orientation_error(const T (&tq)[4], const T (&qc)[4], int angle_f32,
     return;
   }
   const T wc = dw < T(-1) ? T(-1) : (dw > T(1) ? T(1) : dw);
-  T angle = T(2) * (T)acos_branchfree((double)wc);
+  T angle = T(2) * (T)acos_branchfree<UNI>((double)wc);
   // axis = v / sqrt(1 - w^2), renormalised (btQuaternion::getAxis + btVector3::normalize): together v / |v|; the
   // degenerate branch (1 - w^2 < 10 eps -> axis (1,0,0)) is a select so that the whole function is one basic block
   // and its long dependent chain (acos, rsqrt) can be scheduled under the Jacobian / J J^T arithmetic
@@ -657,12 +736,12 @@ AE_DEV bool ik_stop(const IKParams<T> &P, const T (&tgt)[3], const FKState<T> &S
 }
 // SMALL: 1 / 0 = the caller has already branched on small_steps (a compile-time constant here: the lockstep loop tests it once per
 // step instead of once per trip), -1 = the run-time argument decides.
-template <class C, typename T, int MODE = 0, int SMALL = -1>
+template <class C, typename T, int MODE = 0, int SMALL = -1, int UNI = 0>
 AE_DEV void ik_update(const ChainDev<T> &ch, const IKParams<T> &P, T (&q)[NJ], FKState<T> &S, T (&cq)[NJ], T (&sq)[NJ], T (&e)[6],
                       const T (&pe)[3], T diff2, T &diff2_prev, int &it, bool small_steps, T &minpiv) {
   T qc[4], eo[3], dth[NJ];
-  quat_from_frame<T>(S.W, qc);
-  orientation_error<T>(P.tq, qc, P.angle_f32, eo);
+  quat_from_frame<T, UNI>(S.W, qc);
+  orientation_error<T, UNI>(P.tq, qc, P.angle_f32, eo);
   e[3] = eo[0]; e[4] = eo[1]; e[5] = eo[2];
   dls_update<C, T, MODE>(S, pe, e, P, dth, minpiv);
   static_for<0, NJ>([&](auto II) { constexpr int i = II; q[i] += dth[i]; });
@@ -679,12 +758,12 @@ AE_DEV void ik_update(const ChainDev<T> &ch, const IKParams<T> &P, T (&q)[NJ], F
   ++it;
   fk<C, T>(ch, cq, sq, S);
 }
-template <class C, typename T, int MODE = 0, int SMALL = -1>
+template <class C, typename T, int MODE = 0, int SMALL = -1, int UNI = 0>
 AE_DEV bool ik_trip(const ChainDev<T> &ch, const IKParams<T> &P, T (&q)[NJ], const T (&tgt)[3], FKState<T> &S, T (&cq)[NJ],
                     T (&sq)[NJ], T &diff2_prev, int &it, T res2, bool small_steps, T &minpiv) {
   T e[6], pe[3], diff2;
   if (ik_stop<C, T, MODE>(P, tgt, S, diff2_prev, it, res2, e, pe, diff2)) return true;
-  ik_update<C, T, MODE, SMALL>(ch, P, q, S, cq, sq, e, pe, diff2, diff2_prev, it, small_steps, minpiv);
+  ik_update<C, T, MODE, SMALL, UNI>(ch, P, q, S, cq, sq, e, pe, diff2, diff2_prev, it, small_steps, minpiv);
   return false;
 }
 // Bullet's loop for the lanes of a wave walking through it together (the lockstep kernels).  Returns the lane's number of updates.
@@ -706,9 +785,11 @@ AE_DEV int ik_lockstep(const ChainDev<T> &ch, const IKParams<T> &P, T (&q)[NJ], 
   int it = 0;
   // (Branching on small_steps HERE, once per step, with two compile-time copies of the trips behind it, was tried: the second copy
   // of the loop raised the register pressure -- 124 -> 181 AGPRs of spill space in the reach rollout -- and cost 8 %.)
+  // The peeled trips carry the wave-uniform orientation dispatch (ARMENV_UNIFORM_ORIENT above); the loop behind them -- all the trips of
+  // the kernels that peel none: the step kernel with its cold instruction fetch, the fused-actor rollouts -- keeps the select form alone.
   bool stopped = false;
   static_for<0, PEEL>([&](auto) {
-    if (!stopped) stopped = ik_trip<C, T, MODE>(ch, P, q, tgt, S, cq, sq, diff2_prev, it, res2, small_steps, minpiv);
+    if (!stopped) stopped = ik_trip<C, T, MODE, -1, ARMENV_UNIFORM_ORIENT>(ch, P, q, tgt, S, cq, sq, diff2_prev, it, res2, small_steps, minpiv);
   });
   if (!stopped) while (!ik_trip<C, T, MODE>(ch, P, q, tgt, S, cq, sq, diff2_prev, it, res2, small_steps, minpiv)) {}
   return it;
@@ -776,7 +857,7 @@ AE_DEV int ik_move(const ChainDev<T> &ch, const IKParams<T> &P, T (&q)[NJ], T (&
     ik_target<T, START_F32>(S, a, dv, box_lo, box_hi, tgt);
   }
   T minpiv = T(1e30);
-  while (!ik_trip<C, T, MODE>(ch, P, q, tgt, S, cq, sq, diff2_prev, it, res2, small_steps, minpiv)) {}
+  while (!ik_trip<C, T, MODE, -1, ARMENV_UNIFORM_ORIENT>(ch, P, q, tgt, S, cq, sq, diff2_prev, it, res2, small_steps, minpiv)) {}
   const bool hit = ik_limits<C, T, MODE>(ch, P, q, S, cq, sq);
   if (limit_hit) *limit_hit = hit;
   if (cq_io) { static_for<0, NJ>([&](auto JI) { constexpr int j = JI; (*cq_io)[j] = cq[j]; (*sq_io)[j] = sq[j]; }); }
