@@ -40,8 +40,18 @@ struct ActorParams {
 // ------------------------------------------------------------------------------------------------------------------
 // Fast variant: layer 2 on the f16 MFMA (v_mfma_f32_32x32x16_f16, 16x the f32 MFMA rate) with both operands split
 // x = hi + lo, hi = f16(x), lo = f16(x - hi), and three passes  hi*hi + hi*lo + lo*hi  accumulated in f32.  f16 products
-// are exact in f32, so only the lo*lo term (2^-22 relative) and f32 accumulation order separate the result from the
-// exact-f32 path above: within the 1e-5 actor tolerance of the reference's vectors (tests).
+// are exact in f32.  The split is unscaled, so what separates the result from the exact-f32 path above is, per product w x:
+// the split residuals |x - hi - lo| <= max(2^-22 |x|, 2^-25) of both operands (lo is an f16 SUBNORMAL for every |x| < 2^-3 --
+// every W2 entry of a freshly initialised net -- so below 2^-3 the residual is an absolute 2^-25, not 2^-22 relative; the f16
+// MFMA keeps subnormal operands), the dropped lo*lo term (|lo_w| |lo_x|: 2^-22 |w x| when both lo parts are normal), and the
+// f32 accumulation of three times as many terms.  tests/actor_ref64.py derives the per-output bound from these and
+// tests/test_gpu_actor_ref64.py holds all three forwards to it over weight scales 2^-8 .. 2^4 and observations 1e-3 .. 30
+// (measured: at most 0.1 of the bound, profiles/actor_ref64_margins.json); at the reference's initialisation scale the
+// result is within the 1e-5 actor tolerance of the reference's vectors.
+// DOMAIN of the f16x3 paths (this actor and datd3_forward_wg): every value that is split -- W1, b1, W2, the observation, a
+// critic's action inputs and every hidden-1 activation at run time -- must have magnitude <= 65504.  Above, hi = inf,
+// lo = -inf and the output is NaN; nothing checks for it.  b2, W3, b3 and the hidden-2 activations stay f32 and are not limited.
+// The exact-f32 actor has the range of f32.
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 struct ActorParamsH {
