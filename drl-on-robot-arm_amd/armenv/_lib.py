@@ -4,7 +4,7 @@ import ctypes as C
 import os
 
 NJ = 7
-ABI_VERSION = 8
+ABI_VERSION = 9
 TASK_REACH, TASK_PUSH, TASK_PICK = 0, 1, 2
 ROBOT_KUKA, ROBOT_DIANA = 0, 1
 FK_AUTO, FK_GENERIC = 0, 1
@@ -61,7 +61,7 @@ class ArmEnvHerArgs(C.Structure):
         ("obs0_dev", C.c_void_p), ("obs_after_dev", C.c_void_p), ("next_obs_dev", C.c_void_p), ("action_dev", C.c_void_p),
         ("reward_dev", C.c_void_p), ("done_dev", C.c_void_p), ("episodes_dev", C.c_void_p), ("num_episodes_dev", C.c_void_p),
         ("batch", C.c_int64), ("picks_dev", C.c_void_p), ("seed", C.c_uint64), ("draw", C.c_uint64),
-        ("her_ratio", C.c_float), ("dis_threshold", C.c_float),
+        ("her_ratio", C.c_double), ("dis_threshold", C.c_double),
         ("states_dev", C.c_void_p), ("actions_dev", C.c_void_p), ("next_states_dev", C.c_void_p), ("rewards_dev", C.c_void_p),
         ("dones_dev", C.c_void_p), ("picks_out_dev", C.c_void_p),
     ]

@@ -656,7 +656,7 @@ static const char *her_refusal(const ArmEnvHerArgs *a, const ArmEnvHerPopArgs *p
   NEEDS(episodes_dev); NEEDS(num_episodes_dev); NEEDS(states_dev); NEEDS(actions_dev); NEEDS(next_states_dev); NEEDS(rewards_dev);
   NEEDS(dones_dev);
 #undef NEEDS
-  if (!(a->her_ratio >= 0.f && a->her_ratio <= 1.f)) return "her_ratio outside [0,1]";
+  if (!(a->her_ratio >= 0.0 && a->her_ratio <= 1.0)) return "her_ratio outside [0,1]";
   return nullptr;
 }
 

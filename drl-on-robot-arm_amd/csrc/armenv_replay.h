@@ -75,7 +75,7 @@ struct HerArgs {
   const int32_t *picks_in;   // nullable [B][4] = (episode, step_state, use_her, step_goal): teacher-forced draws
   uint64_t seed, draw;
   int32_t use_her;
-  float her_ratio, dis_threshold;
+  double her_ratio, dis_threshold;   // the caller's doubles: the reference compares against Python floats
   float *states, *actions, *next_states, *rewards;
   uint8_t *dones;
   int32_t *picks_out;        // nullable
@@ -106,7 +106,7 @@ AE_DEV void her_sample_one(const HerArgs &A, int64_t b) {
     ep = (int32_t)(u0 * (double)E);                         // random.sample(buffer, 1)      rl_utils.py:126
     const int32_t L = A.episodes[3 * ep + 2];
     st = (int32_t)(u1 * (double)L);                         // np.random.randint(length)     :127
-    her = (A.use_her && u2 <= (double)A.her_ratio) ? 1 : 0; // np.random.uniform() <= ratio  :134
+    her = (A.use_her && u2 <= A.her_ratio) ? 1 : 0; // np.random.uniform() <= ratio  :134
     sg = st + 1 + (int32_t)(u3 * (double)(L - st));         // randint(step+1, length+1)     :135
   }
   const int32_t *e = A.episodes + 3 * ep;
@@ -130,10 +130,10 @@ AE_DEV void her_sample_one(const HerArgs &A, int64_t b) {
     bool far;
     if (D == 9) {   // push observations are float64 in the reference (rl_push_env.py:308): f64 arithmetic
       const double d0 = (double)nv[0] - (double)g0, d1 = (double)nv[1] - (double)g1, d2 = (double)nv[2] - (double)g2;
-      far = ::sqrt((d0 * d0 + d1 * d1) + d2 * d2) > (double)A.dis_threshold;
+      far = ::sqrt((d0 * d0 + d1 * d1) + d2 * d2) > A.dis_threshold;
     } else {        // reach observations are float32: np.sqrt(np.sum(np.square(f32[3])))  :137
       const float d0 = nv[0] - g0, d1 = nv[1] - g1, d2 = nv[2] - g2;
-      far = (double)sqrtf((d0 * d0 + d1 * d1) + d2 * d2) > (double)A.dis_threshold;
+      far = (double)sqrtf((d0 * d0 + d1 * d1) + d2 * d2) > A.dis_threshold;
     }
     r = far ? -0.1f : 1.0f;                                 // :138
     dn = far ? 0 : 1;                                       // :139

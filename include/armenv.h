@@ -35,7 +35,9 @@ extern "C" {
 #endif
 
 #define ARMENV_NJ 7
-#define ARMENV_ABI_VERSION 8   /* 8: + armenv_daddpg_update, armenv_daddpg_workspace_bytes, ArmEnvDaddpgArgs;
+#define ARMENV_ABI_VERSION 9   /* 9: ArmEnvHerArgs.her_ratio and .dis_threshold are double (were float): the sampler compares against the
+                                     caller's own doubles, as the reference compares against Python floats; the struct grew by 8 bytes;
+                                  8: + armenv_daddpg_update, armenv_daddpg_workspace_bytes, ArmEnvDaddpgArgs;
                                      still 8: + armenv_datd3_update, armenv_datd3_workspace_bytes, ArmEnvDatd3Args -- purely additive
                                      (two functions, one struct, nothing existing moves), so the number did not change;
                                      still 8: + armenv_td3_pop_update, armenv_td3_pop_workspace_bytes, ArmEnvTd3PopArgs, additive
@@ -432,8 +434,11 @@ typedef struct ArmEnvHerArgs {
   int64_t batch;                    /* B */
   const int32_t *picks_dev;         /* nullable i32 [B][4] = (episode, step_state, use_her, step_goal): caller-supplied
                                        draws (parity tests feed the reference's own draws); NULL: Philox(seed, draw) */
-  uint64_t seed, draw;
-  float her_ratio, dis_threshold;   /* 0.8 (config.py:80), 0.1 (rl_utils.py:119) */
+  uint64_t seed, draw;              /* the Philox counter of sample b is (b lo, b hi, the LOW 32 BITS of draw, 0 | 1): draws that
+                                       differ by a multiple of 2^32 give the same batch */
+  double her_ratio, dis_threshold;  /* 0.8 (config.py:80), 0.1 (rl_utils.py:119): the caller's doubles, compared as they are
+                                       (u <= her_ratio, dis > dis_threshold; dis is f32 arithmetic for obs_dim 6, f64 for 9).
+                                       Every field is 8 bytes wide or one of the int32 pair above: no padding holes. */
   float *states_dev;                /* out f32 [B][D] */
   float *actions_dev;               /* out f32 [B][3] */
   float *next_states_dev;           /* out f32 [B][D] */

@@ -17,6 +17,8 @@ reference's importable Python (config, algo.TD3) -- never reference source text.
                                envs/rl_reach_env.py:299-309 (strict '>' and '<')
   G6 her_{reach,push}_seed0.npz  ReplayBuffer_Trajectory_{reach,push}.sample outputs + the draws it made
                                (utils/rl_utils.py:108-199), produced by importing the reference
+  G17 her_edges_{reach,push}.npz  the same sample() on the edge cases of tests/her_cases.py (the threshold block and the linear
+                               addressing stores) with its draws FORCED to the table's picks: inputs, picks, thresholds, outputs
   G8 td3_train_seed0.npz       six TD3_MLP.train() updates of the reference: losses + final parameters
                                (algo/TD3/TD3_mlp.py:114-161), produced by importing the reference
   G7 push_reward_truth.json    (cube, target, d_last, step_counter) -> (reward, done, is_success) of
@@ -359,6 +361,73 @@ def g6_her_samples():
                  dones=np.array(outs["dones"], np.uint8))
 
 
+def g17_her_edges():
+    """G17: the reference's ReplayBuffer_Trajectory_{reach,push}.sample on the edge cases of tests/her_cases.py -- the threshold block
+    (distances planted on, one step below and one step above dis_threshold, and where another summation would cross it) and the linear
+    addressing stores (every (episode, step, goal step) of a window with episodes of length 1).  One sample(1, ...) per pick with the
+    draws forced: random.sample, np.random.randint and np.random.uniform return the table's pick.  States are float32 for reach and
+    float64 holding the same float32 values for push (as G6), rewards Python floats.  The threshold is the Python float, handed over
+    as np.float64 (a subclass of float): the reference was written for Python 3.7, hence NumPy 1.x, where `float32 scalar > Python
+    float` compares in float64.  NumPy >= 2 (NEP 50) would round a plain Python float to float32 first -- reach's
+    dis == float32(0.1) would then be near, not far -- and np.float64 keeps the comparison the reference's own environment makes."""
+    sys.path.insert(0, REF)
+    sys.path.insert(0, os.path.dirname(OUT))
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from utils import rl_utils
+    import her_cases as H
+    table = H.build()
+    for task, D, Buf in (("reach", 6, rl_utils.ReplayBuffer_Trajectory_reach), ("push", 9, rl_utils.ReplayBuffer_Trajectory_push)):
+        sdt = np.float32 if D == 6 else np.float64
+        arrays, names = {}, []
+        for S in H.fixture_stores(table, D):
+            lin, eps = H.linear(S), H.episodes_of(S)
+            trajs = []
+            buf = Buf(len(eps))
+            for n, t0, L in eps:
+                first = lin["obs0"][n] if t0 == 0 else lin["obs_after"][t0 - 1, n]
+                traj = rl_utils.Trajectory(first.astype(sdt))
+                for t in range(t0, t0 + L):
+                    traj.store_step(lin["action"][t, n].copy(), lin["next_obs"][t, n].astype(sdt), float(lin["reward"][t, n]), bool(lin["done"][t, n]))
+                buf.add_trajectory(traj); trajs.append(traj)
+            forced = {}
+            o_sample, o_randint, o_uniform = random.sample, np.random.randint, np.random.uniform
+
+            def w_sample(pop, k):
+                assert k == 1 and len(pop) == len(trajs)
+                forced["calls"] = 0
+                return [trajs[forced["ep"]]]
+
+            def w_randint(*a, **kw):
+                forced["calls"] += 1
+                if forced["calls"] == 1:
+                    assert a == (trajs[forced["ep"]].length,)
+                    return forced["st"]
+                assert forced["calls"] == 2 and forced["her"] and a == (forced["st"] + 1, trajs[forced["ep"]].length + 1)
+                return forced["sg"]
+
+            def w_uniform(*a, **kw):
+                return 0.0 if forced["her"] else 2.0
+
+            outs = {k: [] for k in H.BATCH}
+            rl_utils.random.sample, np.random.randint, np.random.uniform = w_sample, w_randint, w_uniform
+            try:
+                for ep, st, h, sg in S["picks"].tolist():
+                    forced.update(ep=ep, st=st, her=h, sg=sg)
+                    b = buf.sample(1, use_her=True, dis_threshold=np.float64(S["thr"]), her_ratio=0.8)
+                    assert forced["calls"] == 1 + h
+                    for k in outs:
+                        outs[k].append(b[k][0])
+            finally:
+                rl_utils.random.sample, np.random.randint, np.random.uniform = o_sample, o_randint, o_uniform
+            names.append(S["name"])
+            arrays.update(H.fixture_arrays(S))
+            ref = dict(states=np.array(outs["states"], np.float64), next_states=np.array(outs["next_states"], np.float64),
+                       actions=np.array(outs["actions"], np.float32), rewards=np.array(outs["rewards"], np.float64),
+                       dones=np.array(outs["dones"], np.uint8))
+            arrays.update({f"{S['name']}/ref.{k}": v for k, v in ref.items()})
+        np.savez(os.path.join(OUT, f"her_edges_{task}.npz"), names=np.array(names), **arrays)
+
+
 def g8_td3_train():
     """G8: six TD3_MLP.train() updates of the reference (algo/TD3/TD3_mlp.py:114-161) from torch.manual_seed(0)
     initialisation on fixed batches: critic losses and the final actor / critic / target parameters."""
@@ -618,6 +687,7 @@ def g16_daddpg_train():
 
 
 if __name__ == "__main__":
+    g17_her_edges()
     g16_daddpg_train()
     g15_daddpg_darc_take_action()
     g14_datd3_take_action_nine_inputs()

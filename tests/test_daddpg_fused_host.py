@@ -15,7 +15,7 @@ def test_daddpg_struct_layout_matches_the_header():
     members = ctypes_layout(L.ArmEnvDaddpgArgs)
     assert {m.split(".")[0] for m, _ in members} >= set(NETS) | {"update_actor", "critic_step", "actor_step", "loss_dev"}
     sizes, offsets = header_layout(L.ArmEnvDaddpgArgs, extra=("ARMENV_ABI_VERSION",))
-    assert sizes[0] == C.sizeof(L.ArmEnvDaddpgArgs) and sizes[1] == L.ABI_VERSION == 8
+    assert sizes[0] == C.sizeof(L.ArmEnvDaddpgArgs) and sizes[1] == L.ABI_VERSION == 9
     assert offsets == [o for _, o in members], members
 
 

@@ -117,7 +117,7 @@ def test_datd3_struct_layout_matches_the_header():
         "update_actor", "darc", "q_weight", "regularization_weight", "policy_noise", "noise_clip", "seed", "draw", "noise_dev",
         "critic_step", "actor_step", "loss_dev"}
     sizes, offsets = header_layout(L.ArmEnvDatd3Args, extra=("ARMENV_ABI_VERSION",))
-    assert sizes[0] == C.sizeof(L.ArmEnvDatd3Args) and sizes[1] == L.ABI_VERSION == 8
+    assert sizes[0] == C.sizeof(L.ArmEnvDatd3Args) and sizes[1] == L.ABI_VERSION == 9
     assert offsets == [o for _, o in members], members
 
 

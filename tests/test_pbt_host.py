@@ -31,7 +31,7 @@ def test_struct_layout_matches_the_header_the_symbol_resolves_and_the_abi_versio
     lib = L.load()
     assert lib.armenv_pop_exploit is not None
     assert L.SYMBOLS["armenv_pop_exploit"] == (C.c_int, [C.POINTER(A), C.c_void_p])
-    assert lib.armenv_abi_version() == 8 and L.ABI_VERSION == 8
+    assert lib.armenv_abi_version() == 9 and L.ABI_VERSION == 9
 
 
 def _args(src=(0, 0, 2), elems=(768, 3, 1), device=0):

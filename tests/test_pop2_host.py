@@ -28,7 +28,7 @@ def test_struct_layout_matches_the_header(algo):
 
 def test_the_abi_version_did_not_move():
     from armenv import _lib as L
-    assert L.load().armenv_abi_version() == 8 and L.ABI_VERSION == 8
+    assert L.load().armenv_abi_version() == 9 and L.ABI_VERSION == 9
 
 
 @pytest.mark.parametrize("algo", ALGOS)

@@ -34,7 +34,7 @@ def test_struct_layout_matches_the_header_and_the_abi_version_did_not_move():
     assert sizes == [C.sizeof(H)] == [32]
     assert [n for n, _ in ctypes_layout(H)] == list(FIELDS) and offsets == [getattr(H, n).offset for n in FIELDS]
     lib = L.load()
-    assert lib.armenv_abi_version() == 8 and L.ABI_VERSION == 8
+    assert lib.armenv_abi_version() == 9 and L.ABI_VERSION == 9
     for stem, pop in (("td3", L.ArmEnvTd3PopArgs), ("daddpg", L.ArmEnvDaddpgPopArgs), ("datd3", L.ArmEnvDatd3PopArgs)):
         res, args = L.SYMBOLS["armenv_%s_pop_update_hyper" % stem]
         assert res is C.c_int and args == [C.POINTER(pop), C.POINTER(H), C.c_void_p]

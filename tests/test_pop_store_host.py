@@ -29,7 +29,7 @@ def test_struct_layout_matches_the_header():
 def test_the_symbols_resolve_and_the_abi_version_did_not_move():
     from armenv import _lib as L
     lib = L.load()
-    assert lib.armenv_abi_version() == 8 and L.ABI_VERSION == 8
+    assert lib.armenv_abi_version() == 9 and L.ABI_VERSION == 9
     for name in ("armenv_her_pop_sample", "armenv_pop_count_episodes", "armenv_pop_write_episodes"):
         assert name in L.SYMBOLS and getattr(lib, name) is not None
 

@@ -22,7 +22,7 @@ def test_struct_layout_matches_the_header():
 
 def test_the_abi_version_did_not_move():
     from armenv import _lib as L
-    assert L.load().armenv_abi_version() == 8
+    assert L.load().armenv_abi_version() == 9
 
 
 @pytest.mark.parametrize("D", [1, 6, 9, 12])
