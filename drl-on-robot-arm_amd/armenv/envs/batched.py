@@ -65,6 +65,7 @@ class BatchedArmEnv:
         self._terminal = None
         self._ik_updates = None
         self._diag = None
+        self._counter_offsets = None  # load_state_dict: what counters() adds to the handle's totals
         self._fixed_stream = None     # set by PipelinedEnv: this handle always launches on its own stream ...
         self._fixed_torch_stream = None   # ... and the same stream as a torch object (ordering against the caller's stream)
         self.action_space = Box(low=[-0.4, -0.4, -0.6], high=[0.4, 0.4, 0.3])       # rl_reach_env.py:87-90
@@ -437,12 +438,50 @@ class BatchedArmEnv:
         return dict(mean_distance=out[0] / n, max_distance=out[1], mean_last_return=out[2] / n, mean_last_len=out[3] / n,
                     last_success_rate=out[4] / n, raw=out)
 
-    def counters(self):
+    def _handle_counters(self):
         out = (C.c_uint64 * 16)()
         L.check(self._lib.armenv_counters(self._h, C.byref(out), self._stream()))
         return dict(episodes=out[0], successes=out[1], env_steps=out[2], nonfinite=out[3], ik_updates=out[4],
                     limit_steps=out[5], low_flange_steps=out[6], cap_steps=out[7], illcond_steps=out[8],
                     wave_trips=out[9], wave_rounds=out[10])
+
+    def counters(self):
+        c = self._handle_counters()
+        if self._counter_offsets:     # after load_state_dict: the totals continue from the saved ones
+            c = {k: v + self._counter_offsets[k] for k, v in c.items()}
+        return c
+
+    def state_dict(self):
+        """What a run needs to continue this handle's trajectories bit for bit, as CPU tensors and plain numbers: every field of
+        ``get_state()`` (``trig`` included) and the totals of ``counters()``."""
+        return dict(kind=type(self).__name__, num_envs=self.num_envs,
+                    fields={k: v.to("cpu") for k, v in self.get_state().items()}, counters=dict(self.counters()))
+
+    def load_state_dict(self, sd):
+        """``set_state(**fields)`` with ``trig``, so that the trajectories continue bit for bit, and host-side offsets so that
+        ``counters()`` continues from the saved totals.  Not restored: the last finished episode's statistics (``episode_stats``,
+        ``episode_returns_f32``, ``summary``), which the engine keeps for logging only -- they are this handle's own until its
+        envs finish an episode again.  ValueError naming the first field that does not fit (kind, num_envs, a field's name or shape)
+        before anything is changed."""
+        who = type(self).__name__
+        for name, mine in (("kind", who), ("num_envs", self.num_envs)):
+            if sd.get(name) != mine:
+                raise ValueError("%s.load_state_dict: %s is %r in the state, %r here" % (who, name, sd.get(name), mine))
+        n, push = self.num_envs, self.task != L.TASK_REACH
+        want = dict(q=((n, 7), torch.float64), step=((n,), torch.int32), episode=((n,), torch.int32), ep_return=((n,), torch.float64),
+                    trig=((n, 14), torch.float64))
+        want.update(aux=((n, self.aux_dim), torch.float64)) if push else want.update(goal=((n, 3), torch.float32))
+        fields = sd["fields"]
+        if sorted(fields) != sorted(want):
+            raise ValueError("%s.load_state_dict: fields are %s in the state, %s here" % (who, sorted(fields), sorted(want)))
+        for k, (shape, dt) in want.items():
+            if not torch.is_tensor(fields[k]) or tuple(fields[k].shape) != shape or fields[k].dtype != dt:
+                raise ValueError("%s.load_state_dict: %s must be a %s tensor of shape %s" % (who, k, dt, shape))
+        now = self._handle_counters()
+        if sorted(sd["counters"]) != sorted(now):
+            raise ValueError("%s.load_state_dict: counters are %s in the state, %s here" % (who, sorted(sd["counters"]), sorted(now)))
+        self.set_state(**fields)
+        self._counter_offsets = {k: int(sd["counters"][k]) - now[k] for k in now}
 
 
 class BatchedReachEnv(BatchedArmEnv):

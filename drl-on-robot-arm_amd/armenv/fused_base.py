@@ -7,6 +7,7 @@ from functools import cached_property
 import torch
 
 from . import _lib as L
+from .checkpoint import AgentFiles, check_field, check_tensors, to_cpu
 
 
 def _mlp(net, heads=("fc1", "fc2", "fc3")):
@@ -27,7 +28,7 @@ def _mlp_of(tensors):
     return m
 
 
-class FusedLearner:
+class FusedLearner(AgentFiles):
     """Base of the fused learners and, through fused_pop_base.FusedPopulation, of their populations.  An agent's schedule class (the
     mixin next to its single learner: fused_td3.TD3Schedule, ...) names the C entry points' argument struct ``_Args``, the
     hyper-parameters ``_hyper`` it copies into the struct beside the common ones, the constructor's hyper-parameters ``_HYPER_KW``
@@ -35,13 +36,18 @@ class FusedLearner:
     armenv_<_fn>_workspace_bytes) and which exception ``_noise_error`` a wrongly shaped ``noise`` raises, and creates its own nets,
     in its torch learner's order.  What a population overrides of the call path: ``_lead``, the shape in front of every tensor -- ()
     here, (P,) there: the loss's shape, what precedes [B][action_dim] in `noise`, and the workspace query's further argument --,
-    ``_batch_axis`` (which axis of the batch is B, ``len(_lead)``) and ``_per_call_struct``."""
+    ``_batch_axis`` (which axis of the batch is B, ``len(_lead)``) and ``_per_call_struct``.
+
+    ``save`` / ``load``: the agent in the reference's files (armenv.checkpoint).  ``state_dict()`` / ``load_state_dict(sd)``: the
+    whole learner -- every net, target and moment tensor, the counters and the noise seed -- as CPU tensors and plain numbers, for a
+    run that is to continue bit for bit; a single learner names its learning nets ``_LEARNING``."""
 
     _fn = _Args = None
     _hyper = _HYPER_KW = _COUNTERS = ()       # _hyper: fields of the C struct; _HYPER_KW: keyword arguments of the constructor
     _takes_seed = False                       # whether the constructor has `seed` (the agent draws target-policy noise)
     _noise_error = ValueError
     _lead, _batch_axis = (), 0
+    _LEARNING = ()                            # a single learner's learning nets: each has a target_<name>, <name>_m and <name>_v
 
     def _check_shapes(self, state_dim, action_dim, hidden_dim):
         if hidden_dim != 256 or action_dim != 3 or not 1 <= state_dim <= 12:
@@ -171,6 +177,52 @@ class FusedLearner:
                     v.zero_()
             setattr(self, name + "_step", step)
         self.total_it = learner.total_it
+
+    # ---- the whole learner's state (armenv.checkpoint)
+    def _state_tensors(self):
+        """name -> the list of this learner's own tensors under it: the nets' and targets' parameters and the moments"""
+        out = {}
+        for name in self._LEARNING:
+            out[name] = list(getattr(self, name).parameters())
+            out["target_" + name] = list(getattr(self, "target_" + name).parameters())
+            out[name + "_m"], out[name + "_v"] = getattr(self, name + "_m"), getattr(self, name + "_v")
+        return out
+
+    def _state_header(self):
+        """the fields that must agree before a state is loaded, in the order they are checked"""
+        return dict(kind=type(self).__name__, state_dim=self.state_dim, action_dim=self.action_dim, hidden_dim=self.hidden_dim)
+
+    def state_dict(self):
+        """The learner's whole state: CPU copies of every net, target and moment tensor, the counters and the seed (None for an
+        agent that draws no noise).  The hyper-parameters are the constructor's and are not part of it."""
+        return dict(self._state_header(), seed=getattr(self, "seed", None), counters={n: int(getattr(self, n)) for n in self._COUNTERS},
+                    tensors={name: [to_cpu(t) for t in ts] for name, ts in self._state_tensors().items()})
+
+    def _check_state(self, sd):
+        who = type(self).__name__
+        for name, value in self._state_header().items():
+            check_field(who, name, sd.get(name), value)
+        check_field(who, "counters", sorted(sd["counters"]), sorted(self._COUNTERS))
+        own = self._state_tensors()
+        check_field(who, "tensors", sorted(sd["tensors"]), sorted(own))
+        for name, ts in own.items():
+            check_tensors(who, name, sd["tensors"][name], ts)
+        if (sd["seed"] is None) != (getattr(self, "seed", None) is None):
+            check_field(who, "seed", sd["seed"], getattr(self, "seed", None))
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        """Restores ``state_dict()``'s state in place; ValueError naming the first field that does not fit (kind, a shape, ...)
+        before anything is changed.  The bound argument struct is dropped: the next ``train`` binds anew."""
+        self._check_state(sd)
+        for name, ts in self._state_tensors().items():
+            for t, s in zip(ts, sd["tensors"][name]):
+                t.copy_(s)
+        for name, value in sd["counters"].items():
+            setattr(self, name, int(value))
+        if sd["seed"] is not None:
+            self.seed = int(sd["seed"])
+        self._args = self._one = None
 
     @torch.no_grad()
     def _take_action_of_two(self, state, critic1, critic2):

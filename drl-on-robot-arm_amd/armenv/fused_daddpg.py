@@ -44,6 +44,7 @@ class FusedDADDPG(DADDPGSchedule, FusedLearner):
     ``take_action``, ``policy_state_dicts()``, ``_nets()``) with the update in HIP; ``load_from`` copies a DADDPG's whole state."""
 
     _fn = "daddpg"
+    _LEARNING = ("actor1", "actor2", "critic")
 
     def __init__(self, state_dim, action_dim, action_bound, hidden_dim=256, actor_lr=1e-3, critic_lr=1e-3, tau=0.005, gamma=0.98,
                  device="cuda:0"):

@@ -74,6 +74,7 @@ class FusedDATD3(DATD3Schedule, FusedLearner):
     proposals of a row receive the same noise); ``noise=`` supplies it instead."""
 
     _fn = "datd3"
+    _LEARNING = _LEARNING
 
     def __init__(self, state_dim, action_dim, action_bound, hidden_dim=256, actor_lr=1e-3, critic_lr=1e-3, tau=0.005, gamma=0.98,
                  policy_noise=0.2, noise_clip=0.5, policy_freq=3, device="cuda:0", seed=0):

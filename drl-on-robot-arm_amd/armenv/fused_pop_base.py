@@ -16,6 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from .checkpoint import AgentFiles, check_field
 from .fused_base import FusedLearner, _mlp_of
 
 MAX_MEMBERS = 64
@@ -59,10 +60,10 @@ def check_plan(who, src, members):
     return plan
 
 
-class TwoActorMember:
+class TwoActorMember(AgentFiles):
     """Member p of a population of two-actor agents: the agent's modules, under the names its single learner gives them, whose
     parameters are views into the population's stacks (what the update writes, they show; what is written through them, the update
-    reads), with the single learner's ``take_action`` and ``policy_state_dicts()``."""
+    reads), with the single learner's ``take_action``, ``policy_state_dicts()`` and ``save`` / ``load`` (through the views)."""
 
     _take_action_of_two = FusedLearner._take_action_of_two
 
@@ -203,6 +204,40 @@ class FusedPopulation(FusedLearner):
                 self._rows[p] = dict(self._rows[plan[p]])
             self._hyper_changed()
         return replaced
+
+    # ---- files and state (armenv.checkpoint)
+    def save(self, filename):
+        """every member p in the reference's files, as ``filename + ".m%d" % p``; returns the files written"""
+        return [path for p in range(self.members) for path in self.member(p).save("%s.m%d" % (filename, p))]
+
+    def load(self, filename):
+        """every member p from the files ``filename + ".m%d" % p``"""
+        for p in range(self.members):
+            self.member(p).load("%s.m%d" % (filename, p))
+
+    def _state_tensors(self):
+        return self.stacks
+
+    def _state_header(self):
+        return dict(super()._state_header(), members=self.members)
+
+    def state_dict(self):
+        """FusedLearner.state_dict with ``stacks`` as the tensors, and the members' hyper-parameter rows"""
+        return dict(super().state_dict(), rows=[dict(row) for row in self._rows])
+
+    def _check_state(self, sd):
+        super()._check_state(sd)
+        who = type(self).__name__
+        check_field(who, "rows", len(sd["rows"]), self.members)
+        for p, row in enumerate(sd["rows"]):
+            check_field(who, "rows[%d]" % p, sorted(row), sorted(self._rows[p]))
+            for name, value in row.items():
+                _check_range(who + ".load_state_dict", name, float(value))
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        self._rows = [{name: float(value) for name, value in row.items()} for row in sd["rows"]]
+        self._hyper_changed()
 
     def _bind(self, args):
         super()._bind(args)

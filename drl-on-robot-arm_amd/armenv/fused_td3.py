@@ -47,6 +47,7 @@ class FusedTD3(TD3Schedule, FusedLearner):
     target-policy noise (Philox4x32-10 over (seed, row, update number)); ``train(batch, noise=...)`` supplies it instead."""
 
     _fn, _noise_error = "td3", AssertionError
+    _LEARNING = ("actor", "critic")
 
     def __init__(self, state_dim, action_dim, action_bound, hidden_dim=256, actor_lr=1e-3, critic_lr=1e-3, tau=0.005,
                  gamma=0.98, policy_noise=0.2, noise_clip=0.5, policy_freq=3, device="cuda:0", seed=0):

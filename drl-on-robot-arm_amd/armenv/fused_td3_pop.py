@@ -9,6 +9,7 @@ Members share the step schedule (total_it, the Adam step numbers, policy_freq) a
 slice of a stack [P][rows][cols] that this object owns; member p's update equals, bit for bit, FusedTD3's with member p's
 hyper-parameters on the same state with seed ``seed + p``."""
 from . import _lib as L
+from .checkpoint import AgentFiles
 from .fused_pop_base import MAX_MEMBERS, FusedPopulation  # noqa: F401  (MAX_MEMBERS: importable from here as before)
 from .fused_td3 import FusedTD3, TD3Schedule
 
@@ -21,10 +22,10 @@ def _six(net, half=0):
     return list(net.parameters())[6 * half:6 * half + 6]
 
 
-class Member:
+class Member(AgentFiles):
     """Member p of a FusedTD3Population: the ``actor`` / ``critic`` / ``target_actor`` / ``target_critic`` modules of a TD3 agent
     whose parameters are views into the population's stacks (what the update writes, they show; what is written through them, the
-    update reads)."""
+    update reads); ``save`` / ``load`` as FusedTD3's, through the views."""
 
     def __init__(self, index, device, nets):
         self.index, self.device = index, device

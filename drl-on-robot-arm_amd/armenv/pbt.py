@@ -59,6 +59,30 @@ class PBTSchedule:
                 raise ValueError("PBTSchedule: %s is not one of the agent's %s" % (name, ", ".join(allowed)))
         return self
 
+    def state_dict(self):
+        """The schedule as plain numbers, strings and lists: the constructor's arguments, the bound names and the generator's
+        state -- what ``step`` will draw next (armenv.checkpoint)."""
+        version, words, gauss = self.rng.getstate()
+        return dict(kind=type(self).__name__, every=self.every, fraction=self.fraction, perturb=list(self.perturb), seed=self.seed,
+                    names=None if self.names is None else list(self.names), rng=[version, list(words), gauss])
+
+    def load_state_dict(self, sd):
+        """Continues the saved schedule's draws: takes its bound names and its generator's state.  The constructor's arguments
+        must be the saved ones: ValueError naming the first that is not, before anything is changed."""
+        for name, mine in (("kind", type(self).__name__), ("every", self.every), ("fraction", self.fraction),
+                           ("perturb", list(self.perturb)), ("seed", self.seed)):
+            if sd.get(name) != mine:
+                raise ValueError("PBTSchedule.load_state_dict: %s is %r in the state, %r here" % (name, sd.get(name), mine))
+        names = None if sd["names"] is None else tuple(sd["names"])
+        for name in names or ():
+            if name not in KNOWN_NAMES:
+                raise ValueError("PBTSchedule.load_state_dict: %s is not one of %s" % (name, ", ".join(KNOWN_NAMES)))
+        version, words, gauss = sd["rng"]
+        state = (int(version), tuple(int(w) for w in words), gauss)
+        random.Random().setstate(state)                      # a malformed state raises here, before this schedule is touched
+        self.names = names
+        self.rng.setstate(state)
+
     def due(self, iteration):
         """whether a PBT step follows iteration `iteration` (counted from 1)"""
         return iteration % self.every == 0

@@ -101,9 +101,9 @@ class _Store:
                     episodes=self._new((cap * N, 3), torch.int32),                                   # bound: one per step
                     num_episodes=self._new((), torch.int64))
 
-    def _allocate(self, N, D):
-        """an empty ring of ``capacity`` steps of N envs with D observations (no row outside the window is ever read)"""
-        cap, f32 = int(self.capacity), torch.float32
+    def _allocate(self, N, D, cap=None):
+        """an empty ring of ``capacity`` (or `cap`) steps of N envs with D observations (no row outside the window is ever read)"""
+        cap, f32 = int(self.capacity if cap is None else cap), torch.float32
         self.chunk = dict(cap=cap, base=0, T=0, N=N, D=D, at_reset=True, obs0=self._new((N, D), f32),
                           obs_after=self._new((cap, N, D), f32), next_obs=self._new((cap, N, D), f32),
                           action=self._new((cap, N, 3), f32), reward=self._new((cap, N), f32),
@@ -147,6 +147,59 @@ class _Store:
         last = r["offsets"][..., -1]                              # i64 _lead: contiguous as it stands where there is one member
         r["num_episodes"] = last if last.is_contiguous() else r["num_episodes"].copy_(last)
         self.chunk = r                                            # T and base moved: the binding goes
+
+    # ---- the store's whole state (armenv.checkpoint)
+    def _ring_spec(self, cap, N, D):
+        """key -> (shape, dtype) of the ring's saved tensors"""
+        lead, f32 = self._lead, torch.float32
+        return dict(obs0=(lead + (N, D), f32), obs_after=(lead + (cap, N, D), f32), next_obs=(lead + (cap, N, D), f32),
+                    action=(lead + (cap, N, 3), f32), reward=(lead + (cap, N), f32), done=(lead + (cap, N), torch.uint8))
+
+    def state_dict(self):
+        """The store's whole state as CPU tensors and plain numbers: the ring's geometry (cap, base, T, N, D, at_reset), obs0 and
+        the five rings, the seed, the draw counter and whether the first append has happened.  The episode index is not part of
+        it: ``load_state_dict`` makes it again from the ring."""
+        r, ring = self._ring, None
+        if r is not None:
+            ring = {k: int(r[k]) for k in ("cap", "base", "T", "N", "D")}
+            ring["at_reset"] = bool(r["at_reset"])
+            ring.update({k: r[k].detach().to("cpu", copy=True) for k in self._ring_spec(0, 0, 0)})
+        return dict(kind=type(self).__name__, members=(self._lead or (None,))[0], capacity=self.capacity, seed=self.seed,
+                    draw=self._draw, started=self._started, ring=ring)
+
+    def load_state_dict(self, sd):
+        """Restores ``state_dict()``'s state in place (the rings are allocated here if they are not yet) and indexes the window
+        anew; the sampler's binding is dropped.  ValueError naming the first field that does not fit -- kind, members, capacity, the
+        ring's N or D where this store already holds one, a tensor's shape -- before anything is changed."""
+        who, own = type(self).__name__, self._ring
+        for name, mine in (("kind", who), ("members", (self._lead or (None,))[0]), ("capacity", self.capacity)):
+            if sd.get(name) != mine:
+                raise ValueError("%s.load_state_dict: %s is %r in the state, %r here" % (who, name, sd.get(name), mine))
+        ring = sd["ring"]
+        if ring is not None:
+            cap, N, D = ring["cap"], ring["N"], ring["D"]
+            if own is not None:
+                for name in ("N", "D"):
+                    if own[name] != ring[name]:
+                        raise ValueError("%s.load_state_dict: %s is %r in the state, %r here" % (who, name, ring[name], own[name]))
+            if not (0 <= ring["base"] < cap and 0 <= ring["T"] <= cap):
+                raise ValueError("%s.load_state_dict: base %r, T %r do not fit cap %r" % (who, ring["base"], ring["T"], cap))
+            for k, (shape, dt) in self._ring_spec(cap, N, D).items():
+                t = ring.get(k)
+                if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt:
+                    raise ValueError("%s.load_state_dict: %s must be a %s tensor of shape %s, not %s %s"
+                                     % (who, k, dt, shape, getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
+            if own is None or own["cap"] != cap or own["obs_after"].device != self.device:
+                own = self._allocate(N, D, cap)
+            for k in self._ring_spec(cap, N, D):
+                own[k].copy_(ring[k])
+            own.update(base=int(ring["base"]), T=int(ring["T"]), at_reset=bool(ring["at_reset"]))
+        self.seed, self._draw, self._started = int(sd["seed"]), int(sd["draw"]), bool(sd["started"])
+        if ring is None:
+            self.chunk = None
+        else:
+            self._ring = own
+            self._index()                                         # counts, offsets, episodes, num_episodes: from the ring
 
     def _batch_spec(self, B):
         """key -> (shape, dtype) of a batch of B rows"""

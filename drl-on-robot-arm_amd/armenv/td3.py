@@ -8,6 +8,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .checkpoint import AgentFiles
+
 
 class _CaptureSafeLinear(torch.autograd.Function):
     """y = x W^T + b whose backward contains no multi-block REDUCTION: the bias gradient is a GEMM with a row of ones.
@@ -87,9 +89,10 @@ class TwinCritic(nn.Module):
                 linear(self.fc6, F.relu(linear(self.fc5, F.relu(linear(self.fc4, x))))))
 
 
-class GraphedLearner:
-    """What the learners of this package share: soft updates, `train(batch)` from a dict of device tensors, and the update replayed
-    from hipGraphs.  A subclass provides `_update(s, a, r, s2, d, flag)` (one update; `flag` selects which of its two variants runs),
+class GraphedLearner(AgentFiles):
+    """What the learners of this package share: soft updates, `train(batch)` from a dict of device tensors, the update replayed
+    from hipGraphs, and ``save(filename)`` / ``load(filename)`` in the reference's files (armenv.checkpoint).  A subclass provides
+    `_update(s, a, r, s2, d, flag)` (one update; `flag` selects which of its two variants runs),
     `_flag()` (the variant of update number self.total_it), `_nets()` and `_opts()` (everything an update may write)."""
 
     tau = 0.005

@@ -12,6 +12,14 @@ batch, as the reference's run() counts them.
     python -m armenv.train --iterations 200 --learner hip      # the fused HIP TD3 update (armenv.fused_td3)
     python -m armenv.train --iterations 200 --algo daddpg --learner fused    # the agent's own fused HIP update (armenv.fused_daddpg)
     python -m armenv.train --iterations 200 --algo datd3 --learner fused     # ... armenv.fused_datd3 (also --algo darc)
+    python -m armenv.train --iterations 100 --learner fused --checkpoint run.ckpt --checkpoint-every 20 --save agent --save-best
+    python -m armenv.train --iterations 200 --learner fused --resume run.ckpt --checkpoint run.ckpt      # the same bits as 200 in one go
+
+``save`` / ``save_best``: the trained agent in the reference's files (armenv.checkpoint.save_agent; main.py:148-154 saves at every
+best success rate).  ``checkpoint`` / ``checkpoint_every`` / ``resume``: the whole run's state -- learner, store, env, the loop's
+variables -- in one file, written after every ``checkpoint_every``-th iteration and after the last; a resumed run (``resume=``, every
+other argument but ``iterations``, ``log_every`` and the paths as in the saved one) continues at the next iteration and equals the
+uninterrupted run bit for bit.  For the fused learners: the torch learner's noise comes from torch's device generator.
 """
 import argparse
 import json
@@ -20,6 +28,8 @@ import time
 import torch
 
 from . import envs
+from .checkpoint import (BestKeeper, add_cli_arguments, check_cli_arguments, check_config, check_loop_arguments, checkpoint_due, load_run,
+                         save_agent, save_run, to_cpu)
 from .replay import TrajectoryStore
 from .daddpg import DADDPG
 from .datd3 import DARC, DATD3
@@ -69,11 +79,22 @@ def _install_policy(env, algo, agent, actor_kind, action_bound, sigma, clip):
         install(*agent.policy_state_dicts(), action_bound=action_bound, noise_sigma=sigma, noise_clip=clip)
 
 
-def _train(Env, state_dim, action_bound, sigma, clip, num_envs, iterations, rollout_steps, updates, batch_size, her_ratio, seed, device,
-           actor_kind, log_every, log, window_steps, minimal_episodes, max_steps, use_graphs, algo, learner):
+def _train(task, sigma, clip, num_envs, iterations, rollout_steps, updates, batch_size, her_ratio, seed, device,
+           actor_kind, log_every, log, window_steps, minimal_episodes, max_steps, use_graphs, algo, learner,
+           checkpoint=None, checkpoint_every=0, resume=None, save=None, save_best=False):
     """The loop behind train_reach and train_push: a task's environment class, state_dim and action_bound (a row of ``_TASKS``) and its
     exploration noise N(0, sigma) clipped at `clip`."""
+    Env, state_dim, action_bound = _TASKS[task]
     _check_learner(algo, learner)
+    check_loop_arguments(learner, checkpoint, checkpoint_every, resume, save, save_best)
+    # every argument that shapes the run: a resumed run must repeat them (checked before anything is created on the device)
+    config = dict(task=task, algo=algo, learner=learner, num_envs=num_envs, rollout_steps=rollout_steps, updates=updates,
+                  batch_size=batch_size, her_ratio=her_ratio, seed=seed, actor_kind=actor_kind, expl_sigma=sigma, window_steps=window_steps,
+                  minimal_episodes=minimal_episodes, max_steps=max_steps)
+    saved = None
+    if resume is not None:
+        saved = load_run(resume)
+        check_config(saved["config"], config)
     torch.manual_seed(seed)
     env = Env(num_envs, device=device, seed=seed, max_steps=max_steps)
     agent, static, use_graphs = _make_agent(algo, learner, state_dim, action_bound, device, batch_size, use_graphs, seed)  # main.py:93
@@ -81,8 +102,18 @@ def _train(Env, state_dim, action_bound, sigma, clip, num_envs, iterations, roll
     obs = env.reset()
     history, bufs = [], {}
     c_prev = env.counters()
+    best = BestKeeper(save) if save_best else None
+    first, wall0 = 0, 0.0
+    if saved is not None:          # continue at iteration saved + 1 with the saved run's objects and variables
+        agent.load_state_dict(saved["agent"])
+        store.load_state_dict(saved["store"])
+        env.load_state_dict(saved["env"])
+        obs, history, c_prev = saved["obs"].to(env.device), saved["history"], saved["c_prev"]
+        first, wall0 = saved["iteration"], saved["wall_s"]
+        if best and saved["best"] is not None:
+            best.load_state_dict(saved["best"])
     t0 = time.perf_counter()
-    for it in range(iterations):
+    for it in range(first, iterations):
         _install_policy(env, algo, agent, actor_kind, action_bound, sigma, clip)
         obs0 = obs.clone()
         out = env.rollout(rollout_steps, None, out=bufs, want_actions=True, want_terminal_obs=True)
@@ -104,16 +135,25 @@ def _train(Env, state_dim, action_bound, sigma, clip, num_envs, iterations, roll
             rate = (c["successes"] - c_prev["successes"]) / max(1, ep)
             c_prev = c
             rec = dict(iteration=it + 1, env_steps=c["env_steps"], episodes=c["episodes"], success_rate=rate,
-                       wall_s=time.perf_counter() - t0)
+                       wall_s=wall0 + (time.perf_counter() - t0))
             history.append(rec)
             log(json.dumps(rec))
+            if best:               # main.py:151-153
+                best.offer(rate, agent)
+        if checkpoint_due(it + 1, iterations, checkpoint, checkpoint_every):
+            save_run(checkpoint, dict(config=config, iteration=it + 1, agent=agent.state_dict(), store=store.state_dict(),
+                                      env=env.state_dict(), obs=to_cpu(obs), history=history, c_prev=c_prev,
+                                      wall_s=wall0 + (time.perf_counter() - t0), best=best.state_dict() if best else None))
+    if save is not None:
+        save_agent(agent, save)
     env.close()
     return agent, history
 
 
 def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, batch_size=2048, her_ratio=0.8, seed=0,
                 device="cuda:0", actor_kind="actor_f16x3", expl_sigma=0.7 * 0.98, log_every=10, log=print,
-                window_steps=1536, minimal_episodes=5, max_steps=500, use_graphs=True, algo="td3", learner="torch"):
+                window_steps=1536, minimal_episodes=5, max_steps=500, use_graphs=True, algo="td3", learner="torch",
+                checkpoint=None, checkpoint_every=0, resume=None, save=None, save_best=False):
     # learner="hip": the TD3 update is libarmenv's fused one (armenv.fused_td3.FusedTD3), issued directly: no capture, no graph.
     # learner="fused": the agent's own fused update -- FusedTD3 for td3, armenv.fused_daddpg.FusedDADDPG for daddpg,
     # armenv.fused_datd3.FusedDATD3 / FusedDARC for datd3 / darc.
@@ -123,21 +163,27 @@ def train_reach(num_envs=1024, iterations=200, rollout_steps=32, updates=48, bat
     # initialise their semaphores with one, so every captured bias gradient went wrong from the second replay on.  The captured update
     # now contains no such reduction (armenv.td3._CaptureSafeLinear; profiles/r06_td3_hipgraph_learning.txt) and learns like the eager one.
     # Exploration noise N(0, expl_sigma) clipped at the action bound, 0.7.
-    Env, state_dim, action_bound = _TASKS["reach"]
-    return _train(Env, state_dim, action_bound, expl_sigma, action_bound, num_envs, iterations, rollout_steps, updates, batch_size,
-                  her_ratio, seed, device, actor_kind, log_every, log, window_steps, minimal_episodes, max_steps, use_graphs, algo, learner)
+    # checkpoint, checkpoint_every, resume, save, save_best: the module's docstring.
+    action_bound = _TASKS["reach"][2]
+    return _train("reach", expl_sigma, action_bound, num_envs, iterations, rollout_steps, updates, batch_size,
+                  her_ratio, seed, device, actor_kind, log_every, log, window_steps, minimal_episodes, max_steps, use_graphs, algo, learner,
+                  checkpoint, checkpoint_every, resume, save, save_best)
 
 
 def train_push(num_envs=1024, iterations=300, rollout_steps=32, updates=48, batch_size=2048, her_ratio=0.8, seed=0,
                device="cuda:0", actor_kind="actor_f16x3", log_every=10, log=print, window_steps=1536, minimal_episodes=5,
-               max_steps=500, task="push", use_graphs=True, algo="td3", learner="torch"):
+               max_steps=500, task="push", use_graphs=True, algo="td3", learner="torch",
+               checkpoint=None, checkpoint_every=0, resume=None, save=None, save_best=False):
     """``train_push_with_TD3`` (/root/reference/main.py:449-515) on the device: state_dim 9, action_bound 0.4 (:455-457),
     unclipped exploration noise N(0, 0.4 * 0.98) (:484), push HER relabel rule (utils/rl_utils.py:171-188).  The cube
     follows the build's simplified push-out model, so learning curves are not comparable with the reference's.
-    ``task="pick"`` is ``train_pick_with_TD3`` (main.py:518-585), the same loop around RLPickEnv."""
-    Env, state_dim, action_bound = _TASKS["push" if task == "push" else "pick"]
-    return _train(Env, state_dim, action_bound, action_bound * 0.98, 1e9, num_envs, iterations, rollout_steps, updates, batch_size,
-                  her_ratio, seed, device, actor_kind, log_every, log, window_steps, minimal_episodes, max_steps, use_graphs, algo, learner)
+    ``task="pick"`` is ``train_pick_with_TD3`` (main.py:518-585), the same loop around RLPickEnv.  ``checkpoint``, ``checkpoint_every``,
+    ``resume``, ``save``, ``save_best``: as train_reach's."""
+    task = "push" if task == "push" else "pick"
+    action_bound = _TASKS[task][2]
+    return _train(task, action_bound * 0.98, 1e9, num_envs, iterations, rollout_steps, updates, batch_size,
+                  her_ratio, seed, device, actor_kind, log_every, log, window_steps, minimal_episodes, max_steps, use_graphs, algo, learner,
+                  checkpoint, checkpoint_every, resume, save, save_best)
 
 
 def main():
@@ -158,15 +204,18 @@ def main():
     ap.add_argument("--learner", default="torch", choices=["torch", "hip", "fused"],
                     help="torch: the agent's update in torch (default); hip: libarmenv's fused TD3 update (--algo td3 only); "
                          "fused: the agent's own fused HIP update (FusedTD3, FusedDADDPG, FusedDATD3 or FusedDARC)")
+    add_cli_arguments(ap)
     a = ap.parse_args()
+    check_cli_arguments(ap, a, a.learner)
+    files = dict(checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every, resume=a.resume, save=a.save, save_best=a.save_best)
     if a.task != "reach":
         train_push(a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed, actor_kind=a.actor,
                    window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, use_graphs=a.graphs == 1, algo=a.algo,
-                   learner=a.learner)
+                   learner=a.learner, **files)
         return
     train_reach(a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed, actor_kind=a.actor,
                 expl_sigma=a.sigma, window_steps=a.window_steps, max_steps=a.max_steps, algo=a.algo,
-                use_graphs=a.graphs == 1, learner=a.learner)
+                use_graphs=a.graphs == 1, learner=a.learner, **files)
 
 
 if __name__ == "__main__":

@@ -30,11 +30,20 @@ member, kept for A/B runs (``--store``).
 
 Lockstep rule: the members share the step schedule, so an iteration runs its updates only when EVERY member's store is ready (holds
 ``minimal_episodes`` complete episodes); while one member is not, no member is updated.  The members' stores fill at about the same
-rate, so this delays the first update by a few iterations at most."""
+rate, so this delays the first update by a few iterations at most.
+
+Stopping and continuing (armenv.checkpoint): ``checkpoint`` / ``checkpoint_every`` (``--checkpoint FILE --checkpoint-every N``) write
+the whole run's state -- the population, the store(s), every env, the PBT schedule, the members' sigmas, the loop's variables -- after
+every N-th iteration (after its PBT step) and after the last; ``resume`` (``--resume FILE``, every other argument but ``iterations``,
+``log_every`` and the paths as in the saved run) continues at the next iteration and equals the uninterrupted run bit for bit, PBT
+steps included.  ``save`` (``--save NAME``): every trained member p in the reference's files ``NAME.m<p>_actor.pt``, ...; with
+``save_best`` also as ``NAME.m<p>.best_...`` whenever that member's logged success rate reaches its best."""
 import argparse
 import json
 import time
 
+from .checkpoint import (BestKeeper, add_cli_arguments, check_cli_arguments, check_config, check_loop_arguments, checkpoint_due, load_run,
+                         save_run, to_cpu)
 from .fused_daddpg_pop import FusedDADDPGPopulation
 from .fused_datd3_pop import FusedDARCPopulation, FusedDATD3Population
 from .fused_td3_pop import FusedTD3Population
@@ -80,7 +89,7 @@ def _checked_pbt(pbt, algo, members, seed=0):
 def train_reach_population(members=16, num_envs=64, iterations=200, rollout_steps=32, updates=40, batch_size=256, her_ratio=0.8,
                            seed=0, device="cuda:0", actor_kind="actor_f16x3", expl_sigma=None, log_every=10, log=print,
                            window_steps=1536, minimal_episodes=5, max_steps=500, task="reach", algo="td3", store="population",
-                           sweep=None, pbt=None):
+                           sweep=None, pbt=None, checkpoint=None, checkpoint_every=0, resume=None, save=None, save_best=False):
     """Returns (population, history); a history record holds the members' success rates over the last ``log_every`` iterations.
     ``task="push" | "pick"``: armenv.train.train_push's settings (state_dim 9, action_bound 0.4, unclipped exploration noise).
     ``algo``: the agent; the two-actor agents explore as armenv.train has them explore on that task (the same sigma and clip).
@@ -91,7 +100,9 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
     population-based training over the members, which must be two at least; checked, like ``sweep``, before anything is created on
     the device.  The history then also holds one ``kind="pbt"`` record per PBT step -- iteration, the fitness (success rates since
     the last step), ``src`` and the replaced members' new values -- and every record holds the members' current values as
-    ``hyper``.  Without it the loop, the records and the trained bits are what they are without the argument."""
+    ``hyper``.  Without it the loop, the records and the trained bits are what they are without the argument.
+    ``checkpoint``, ``checkpoint_every``, ``resume``, ``save``, ``save_best``: the module's docstring; a `resume` whose saved arguments
+    are not this call's raises ValueError naming the first that differs, before anything is created on the device."""
     if task not in _TASKS:
         raise ValueError("task must be one of %s" % ", ".join(_TASKS))
     if algo not in ALGOS:
@@ -104,6 +115,16 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
     P = int(members)
     sweep = _checked_sweep(sweep, algo, P)
     pbt = _checked_pbt(pbt, algo, P, seed)
+    check_loop_arguments("fused", checkpoint, checkpoint_every, resume, save, save_best)
+    # every argument that shapes the run: a resumed run must repeat them
+    config = dict(task=task, algo=algo, learner="fused", members=P, num_envs=num_envs, rollout_steps=rollout_steps, updates=updates,
+                  batch_size=batch_size, her_ratio=her_ratio, seed=seed, actor_kind=actor_kind, expl_sigma=sigma, window_steps=window_steps,
+                  minimal_episodes=minimal_episodes, max_steps=max_steps, store=store, sweep=sweep,
+                  pbt=None if pbt is None else {k: v for k, v in pbt.state_dict().items() if k != "rng"})
+    saved = None
+    if resume is not None:
+        saved = load_run(resume)
+        check_config(saved["config"], config)
     sigmas = list(sweep.get("expl_sigma", [sigma] * P))
     pop = _POPULATIONS[algo](P, state_dim, 3, action_bound, device=device, seed=seed,
                              **{name: values for name, values in sweep.items() if name != "expl_sigma"})
@@ -131,8 +152,27 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
         names = [n for n in sweepable_names(algo) if n in sweep or n in pbt.names]
         return {n: [row[n] for row in rows()] for n in names}
 
+    bests = [BestKeeper("%s.m%d" % (save, p)) for p in range(P)] if save_best else None
+    first, wall0 = 0, 0.0
+    if saved is not None:          # continue at iteration saved + 1 with the saved run's objects and variables
+        pop.load_state_dict(saved["population"])
+        if store == "population":
+            pstore.load_state_dict(saved["stores"][0])
+        else:
+            for st, sd in zip(stores, saved["stores"]):
+                st.load_state_dict(sd)
+            obs = [t.to(e.device) for t, e in zip(saved["obs"], es)]
+        for e, sd in zip(es, saved["envs"]):
+            e.load_state_dict(sd)
+        if pbt:
+            pbt.load_state_dict(saved["pbt"])
+        sigmas[:] = saved["sigmas"]
+        prev, prev_pbt, history = saved["prev"], saved["prev_pbt"], saved["history"]
+        first, wall0 = saved["iteration"], saved["wall_s"]
+        for keeper, sd in zip(bests or (), saved["bests"] or ()):
+            keeper.load_state_dict(sd)
     t0 = time.perf_counter()
-    for it in range(iterations):
+    for it in range(first, iterations):
         if store == "population":
             for p, e in enumerate(es):
                 _install_policy(e, algo, pop.member(p), actor_kind, action_bound, sigmas[p], noise_clip)
@@ -163,13 +203,15 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
             rates = [(c["successes"] - c0["successes"]) / max(1, c["episodes"] - c0["episodes"]) for c, c0 in zip(cs, prev)]
             prev = cs
             rec = dict(iteration=it + 1, env_steps=sum(c["env_steps"] for c in cs), episodes=[c["episodes"] for c in cs],
-                       success_rate=rates, wall_s=time.perf_counter() - t0)
+                       success_rate=rates, wall_s=wall0 + (time.perf_counter() - t0))
             if pbt:
                 rec["hyper"] = current()
             elif sweep:
                 rec["hyper"] = sweep
             history.append(rec)
             log(json.dumps(rec))
+            for p, keeper in enumerate(bests or ()):      # main.py:151-153, per member
+                keeper.offer(rates[p], pop.member(p))
         if pbt and pbt.due(it + 1):
             cs = [e.counters() for e in es]
             fitness = [(c["successes"] - c0["successes"]) / max(1, c["episodes"] - c0["episodes"]) for c, c0 in zip(cs, prev_pbt)]
@@ -185,6 +227,15 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
                        hyper=current())
             history.append(rec)
             log(json.dumps(rec))
+        if checkpoint_due(it + 1, iterations, checkpoint, checkpoint_every):
+            save_run(checkpoint, dict(config=config, iteration=it + 1, population=pop.state_dict(),
+                                      stores=[st.state_dict() for st in ([pstore] if store == "population" else stores)],
+                                      envs=[e.state_dict() for e in es], pbt=pbt.state_dict() if pbt else None, sigmas=list(sigmas),
+                                      prev=prev, prev_pbt=prev_pbt, obs=[to_cpu(t) for t in obs], history=history,
+                                      wall_s=wall0 + (time.perf_counter() - t0),
+                                      bests=[k.state_dict() for k in bests] if bests else None))
+    if save is not None:
+        pop.save(save)
     for e in es:
         e.close()
     return pop, history
@@ -213,7 +264,9 @@ def main():
                          "their hyper-parameters")
     ap.add_argument("--pbt-fraction", type=float, default=0.25, metavar="F", help="the bottom's (and the top's) share of the members, in (0, 0.5]")
     ap.add_argument("--pbt-perturb", default="0.8,1.2", metavar="LO,HI", help="the two factors a perturbed value is multiplied by")
+    add_cli_arguments(ap)
     a = ap.parse_args()
+    check_cli_arguments(ap, a, "fused")
     pbt = None
     if a.pbt_every is not None:
         try:
@@ -234,7 +287,8 @@ def main():
         ap.error(str(e))
     train_reach_population(a.members, a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed,
                            actor_kind=a.actor, window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, algo=a.algo, store=a.store,
-                           sweep=sweep or None, pbt=pbt)
+                           sweep=sweep or None, pbt=pbt, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every, resume=a.resume,
+                           save=a.save, save_best=a.save_best)
 
 
 if __name__ == "__main__":
