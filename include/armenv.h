@@ -281,7 +281,8 @@ int armenv_reset_with_goal(ArmEnv *env, const uint8_t *mask_dev, const float *go
  * rounded to f32: [0..2] the end-effector position of getLinkState(...)[4] (:271) -- the very numbers this step's distance,
  * done and success flags come from -- and [3] the reward as a double (the reference returns a Python float).
  * ik_updates_dev and diag_dev are diagnostics: only on a handle created with fence_counters >= 1 (ik_updates_dev) / = 2
- * (diag_dev); ARMENV_ESTATE otherwise. */
+ * (diag_dev); ARMENV_ESTATE otherwise.
+ * NaN, +-inf and huge actions or states: INTEGRATION.md section 5 (one bad env stays one bad env; +-inf clips to the box). */
 int armenv_step(ArmEnv *env, const float *action_dev, float *obs_dev, float *reward_dev, uint8_t *done_dev,
                 uint8_t *success_dev, float *terminal_obs_dev, uint8_t *ik_updates_dev, double *diag_dev, void *stream);
 
@@ -297,7 +298,8 @@ int armenv_step(ArmEnv *env, const float *action_dev, float *obs_dev, float *rew
  *   as in armenv_step, per step.
  * Waves never synchronise inside the launch, so an env that needs extra IK iterations in one step stalls only its own
  * wavefront for that step (lockstep schedule) or only itself (lane-asynchronous schedule, ArmEnvConfig.rollout_ready_lanes):
- * throughput follows the mean IK cost per step, not the per-launch maximum. */
+ * throughput follows the mean IK cost per step, not the per-launch maximum.
+ * Non-finite inputs: as armenv_step, with the same bits and counters under every schedule. */
 int armenv_rollout(ArmEnv *env, int32_t steps, const float *actions_dev, float *obs_dev, float *reward_dev,
                    uint8_t *done_dev, uint8_t *success_dev, float *actions_out_dev, float *terminal_obs_dev,
                    uint8_t *ik_updates_dev, double *diag_dev, void *stream);
@@ -339,7 +341,8 @@ int armenv_episode_stats(ArmEnv *env, double *last_return_dev, int32_t *last_len
 int armenv_episode_returns_f32(ArmEnv *env, float *last_return_dev, void *stream);
 
 /* Totals since creation, copied to host (synchronises `stream`), out[16]: out[0] episodes finished, out[1] successes,
- * out[2] env-steps executed, out[3] non-finite joint states seen, out[4] IK (DLS) updates applied, out[5] env steps whose IK
+ * out[2] env-steps executed, out[3] non-finite joint states seen ((env, step) pairs whose joint angles are not all finite after the
+ * step's IK, before an in-place reset; joint angles only -- not goals, cube state, observations: INTEGRATION.md section 5), out[4] IK (DLS) updates applied, out[5] env steps whose IK
  * result left the URDF joint limits, out[6] env steps that ended with the flange below fence_z, out[7] env steps whose IK
  * call ran to ik_max_iters, out[8] env steps whose IK call passed through an ill-conditioned system (fence_pivot);
  * out[5..8]: the parity fence, counted only with ArmEnvConfig.fence_counters.  Also only with fence_counters, for
@@ -362,7 +365,8 @@ int armenv_summary(ArmEnv *env, double *out_dev, void *stream);
  * Weights are DEVICE pointers in torch Linear layout ([out][in], f32) and are copied.
  * policy = ARMENV_POLICY_RANDOM ignores the weights (zero actor, noise only); ARMENV_POLICY_EXTERNAL removes the
  * fused policy.  The noise of (env, episode, step) is Philox block 0x80000000|step of that env's stream, Box-Muller
- * in f32, so it does not depend on launch geometry, sharding or how steps are grouped into rollouts. */
+ * in f32, so it does not depend on launch geometry, sharding or how steps are grouped into rollouts.
+ * Whatever the weights or the observation hold (NaN, +-inf), the action is finite and within +-noise_clip. */
 int armenv_set_policy(ArmEnv *env, int32_t policy, const float *W1_dev, const float *b1_dev, const float *W2_dev,
                       const float *b2_dev, const float *W3_dev, const float *b3_dev, int32_t hidden_dim,
                       float action_bound, float noise_sigma, float noise_clip, void *stream);
@@ -380,7 +384,8 @@ typedef struct ArmEnvMlp {
  * run inside the rollout kernel as four passes of the f16x3 MFMA actor (f32 emulated by three f16 passes, ~1e-6 of f32; the
  * arg-max can differ from an f32 evaluation only where |q1 - q2| is of that order).  actors: in = obs_dim, out = 3, tanh x
  * action_bound; critics: in = obs_dim + 3, out = 1, no output activation (obs_dim 6 reach, 9 push / pick).  The weights are copied.
- * hidden_dim 256; num_envs must be a multiple of 64; not on a bookkeeping handle (fence_counters). */
+ * hidden_dim 256; num_envs must be a multiple of 64; not on a bookkeeping handle (fence_counters).
+ * Non-finite weights or observations: the action stays finite and within +-noise_clip. */
 int armenv_set_policy_datd3(ArmEnv *env, const ArmEnvMlp *actor1, const ArmEnvMlp *actor2, const ArmEnvMlp *critic1,
                             const ArmEnvMlp *critic2, int32_t hidden_dim, float action_bound, float noise_sigma, float noise_clip,
                             void *stream);
@@ -391,7 +396,7 @@ int armenv_set_policy_datd3(ArmEnv *env, const ArmEnvMlp *actor1, const ArmEnvMl
  * -- the selection rule of armenv_set_policy_datd3 (`>=`: a tie takes actor 1) with ONE critic valuing both proposals: three networks
  * are packed and staged, and the critic's second pass runs on the tables and the W2 ring its first pass left in LDS.
  * DARC_MLP.take_action (/root/reference/algo/DARC/DARC_mlp.py:92-113) is DATD3's, two critics: install it with
- * armenv_set_policy_datd3.  armenv_datd3_forward serves all three. */
+ * armenv_set_policy_datd3.  armenv_datd3_forward serves all three.  Non-finite weights or observations: as armenv_set_policy_datd3. */
 int armenv_set_policy_daddpg(ArmEnv *env, const ArmEnvMlp *actor1, const ArmEnvMlp *actor2, const ArmEnvMlp *critic,
                              int32_t hidden_dim, float action_bound, float noise_sigma, float noise_clip, void *stream);
 
