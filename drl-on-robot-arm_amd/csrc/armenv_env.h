@@ -327,8 +327,10 @@ AE_DEV SinCos sincos_2pi(float u) {
 
 // Three N(0,1) draws for (env, episode, step): Philox block 0x80000000|step of the env's stream (reset draws use
 // blocks < 2^31), Box-Muller in f32 on u = (w + 1) * 2^-32 in (0, 1]: r = sqrt(-2 ln u) through v_log_f32 / v_sqrt_f32 (1 ulp each),
-// the angle through sincos_2pi -- within 3e-7 relative of the libm forms (logf, sqrtf, cosf / sinf of 2 pi u) the parity tests hold
-// the stream against.
+// the angle through sincos_2pi.  Accuracy: tests/noise_ref.py derives a per-output bound from these statements term by term (6.5 to
+// 8.2 times 2^-24 relative to the float64 value of the same f32 uniforms, true zeros included) and tests/test_gpu_noise_ref.py holds
+// every call site to it; the measured margins are in profiles/policy_noise_margins.json.  u = 1 (w >= 0xFFFFFF80) gives
+// log2 = 0, r = sqrt(-0) = -0 and a draw of +-0; u1 = 1 takes k = 4, the angle 0 again.
 AE_DEV void policy_noise(uint64_t seed, uint64_t env_id, uint32_t episode, uint32_t step, float (&nz)[3]) {
   uint32_t c[4] = {(uint32_t)env_id, (uint32_t)(env_id >> 32), episode, 0x80000000u | step};
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
