@@ -3,7 +3,8 @@
 consumption of Python's global ``random`` (6 draws per placement try :197-209, 3 unused draws per step :435-437).
 The arm pipeline, the cube and the reward logic run in the HIP kernels.  The cube's free fall after reset() is Bullet's (pinned
 by the reference's recorded runs); its contact with the tool is ArmEnvConfig.push_contact_model's stand-in for Bullet's rigid-body
-step over the KUKA meshes (not parity-checkable here)."""
+step over the KUKA meshes (not parity-checkable here).
+``_RLCubeEnv`` is what this class and ``RLPickEnv`` (rl_pick_env.py) share; line numbers in it are rl_push_env.py's."""
 import math
 import random
 
@@ -33,19 +34,23 @@ def draw_push_placement():
     return [xpos, ypos, 0.01], [xt, yt, 0.01]
 
 
-class RLPushEnv:
+class _RLCubeEnv:
+    """The N=1 class of a cube task over its batched engine.  A subclass names the engine class and the placement draw."""
     metadata = {'render.modes': ['human', 'rgb_array'], 'video.frames_per_second': 50}
+    _Engine = None
+    _draw_placement = None
+    _obs_z = 0          # offset of the observation box in z (pick: the gripper's length)
 
     def __init__(self, is_render=False, is_good_view=False, device="cuda:0"):
         self.is_render, self.is_good_view = is_render, is_good_view
         self.max_steps_one_episode = opt.max_steps_one_episode                  # :62
         self.distance_threshold = 0.05                                          # :85
         self.action_space = Box(low=[-0.4, -0.4, -0.6], high=[0.4, 0.4, 0.3])  # :94-97
-        self.observation_space = Box(low=[0.2, -0.3, 0], high=[0.7, 0.3, 0.55])  # :100-103
+        self.observation_space = Box(low=[0.2, -0.3, 0 + self._obs_z], high=[0.7, 0.3, 0.55 + self._obs_z])  # :100-103
         self.step_counter = 0
-        self._eng = BatchedPushEnv(1, device=device, auto_reset=False, precision=64, fk_path=1,
-                                   fence_counters=2,
-                                   max_steps=int(self.max_steps_one_episode))
+        self._eng = self._Engine(1, device=device, auto_reset=False, precision=64, fk_path=1,
+                                 fence_counters=2,
+                                 max_steps=int(self.max_steps_one_episode))
         self.seed()
         self.reset()                                                            # :137
 
@@ -60,10 +65,10 @@ class RLPushEnv:
 
     def reset(self):
         self.step_counter = 0
-        cube, target = draw_push_placement()
+        cube, target = self._draw_placement()
         # the cube is spawned at z = 0.01 (the placement test above sees it there); its height is the engine's from there on: one
-        # step into its fall after reset()'s own stepSimulation (:241), on the table 13 steps later (ArmEnvConfig.push_contact_model);
-        # the target is a fixed body and stays
+        # step into its fall after reset()'s own stepSimulation (:241), on the table 13 stepSimulation calls later (push: one per env
+        # step; pick: two, rl_pick_env.py:348 and :417; ArmEnvConfig.push_contact_model); the target is a fixed body and stays
         goal = torch.tensor([cube + target], dtype=torch.float64).to(torch.float32)
         obs = self._eng.reset(goal=goal)[0].cpu().numpy()
         # keep the f64 placement exactly (the engine's reset_with_goal takes f32)
@@ -75,7 +80,7 @@ class RLPushEnv:
         return self._obs64(obs)
 
     def step(self, action):
-        """One armenv_step launch.  Reward, done and is_success are the kernel's (push_step's f64 diagnostics, armenv_step diag_dev:
+        """One armenv_step launch.  Reward, done and is_success are the kernel's (the step's f64 diagnostics, armenv_step diag_dev:
         the C ABI's reward buffer is f32, the reference returns a Python float computed in f64 -- the shaped -100 * (d_now - d_last)
         of :388-397 / :427 with d_last carried in the engine's state, +100 on success :422-424, the float32-state time-limit reward
         :400 / :418-420); nothing of the reward is computed on the host."""
@@ -94,3 +99,8 @@ class RLPushEnv:
 
     def close(self):
         self._eng.close()
+
+
+class RLPushEnv(_RLCubeEnv):
+    _Engine = BatchedPushEnv
+    _draw_placement = staticmethod(draw_push_placement)

@@ -93,13 +93,16 @@ AE_DEV int64_t lane_env(const EnvParams<T> &P) {
   if (!P.half_waves) return t;
   return (t & 32) ? (int64_t)-1 : ((t >> 6) << 5) + (t & 31);
 }
+// A lane's event counts of one launch.
+struct LaneCounts {
+  uint32_t done = 0, succ = 0, bad = 0, upd = 0;
+  uint32_t lim = 0, low = 0, cap = 0, cond = 0;   // parity fence: steps the IK left the URDF limits / ended with the flange below fence_z / ran to the iteration cap / was ill-conditioned
+};
 template <typename T>
-AE_DEV void flush_counts(const EnvParams<T> &P, int64_t i, uint32_t n_done, uint32_t n_succ, uint32_t n_bad, uint32_t n_upd,
-                         uint32_t n_lim, uint32_t n_low, uint32_t n_cap, uint32_t n_cond) {
-  (void)i;
+AE_DEV void flush_counts(const EnvParams<T> &P, const LaneCounts &n) {
   unsigned long long *row = P.counters + kCounterCols * wave_row();
-  const uint32_t d = wave_sum(n_done), s = wave_sum(n_succ), b = wave_sum(n_bad), u = wave_sum(n_upd);
-  const uint32_t l = wave_sum(n_lim), z = wave_sum(n_low), c = wave_sum(n_cap), k = wave_sum(n_cond);
+  const uint32_t d = wave_sum(n.done), s = wave_sum(n.succ), b = wave_sum(n.bad), u = wave_sum(n.upd);
+  const uint32_t l = wave_sum(n.lim), z = wave_sum(n.low), c = wave_sum(n.cap), k = wave_sum(n.cond);
   if ((threadIdx.x & 63) == 0) {   // lane 0 of a launched wave is always a live env (i < N is a prefix)
     if (d) row[0] += d;
     if (s) row[1] += s;
@@ -343,6 +346,55 @@ AE_DEV void policy_noise(uint64_t seed, uint64_t env_id, uint32_t episode, uint3
   nz[0] = r0 * a0.c; nz[1] = r0 * a0.s; nz[2] = r1 * a1.c;
 }
 
+// ---- what the lanes share -------------------------------------------------------------------------------------------
+// ReachLane and CubeLane below carry the same arm -- q, (cq, sq), S, step, ep_ret, cur_obs, minpiv, cnt (the fields are explained at
+// ReachLane).  Written once here, as functions over either lane L, is what could be shared with every kernel keeping the parent
+// build's registers, scratch and loops (tests/tools/kernels_unchanged.py, profiles/lanes_once_isa.txt).  The second half of
+// step_tail, the row-t StepIO of the rollout kernels and their exploration action could not -- shared forms of them moved the cube
+// lanes' two-wave asynchronous kernels and the reach rollouts to more spills or registers -- so the two lanes' step_tail must still
+// be edited as twins from the reward on.
+template <class L, typename T> AE_DEV void lane_make_frame(L &l, const EnvParams<T> &P) {
+  fk<typename L::Chain, T>(P.chain, l.cq, l.sq, l.S);
+}
+// eef of the current state, for the first policy call of a launch (later ones reuse the step's exit FK)
+template <class L, typename T> AE_DEV void lane_refresh_obs(L &l, const EnvParams<T> &P) {
+  FKState<T> F;
+  fk<typename L::Chain, T>(P.chain, l.cq, l.sq, F);
+  l.cur_obs[0] = (float)F.p[0]; l.cur_obs[1] = (float)F.p[1]; l.cur_obs[2] = (float)F.p[2];
+}
+
+// Top of step_tail: the step's IK in the launch's counts.
+template <class L, typename T>
+AE_DEV void lane_count_ik(L &l, const EnvParams<T> &P, int64_t i, const StepIO &io, int updates, bool lim_hit) {
+  l.cnt.upd += (uint32_t)updates;
+  if constexpr (L::kFence) {
+    l.cnt.lim += lim_hit ? 1u : 0u; l.cnt.low += (l.S.p[2] < P.fence_z) ? 1u : 0u; l.cnt.cap += (updates >= P.ik.max_iters) ? 1u : 0u;
+    l.cnt.cond += (l.minpiv < P.ik.fence_pivot) ? 1u : 0u;
+    // the per-step view of the update / cap counts.  Only in the bookkeeping builds: as a nullable pointer of the default
+    // kernels it stayed live in two scalar registers across the IK loop, whose f64 constants were then rematerialised on
+    // every trip (+7 scalar instructions per trip, +1.3 % on the headline; A/B against the round-2 tree)
+    if (io.updates) io.updates[i] = (uint8_t)(updates > 255 ? 255 : updates);
+  }
+}
+// The lockstep step: step_begin, the IK trips (:244-257 of rl_reach_env.py, :339-347 of the cube tasks), step_tail.  Returns the
+// number of IK updates.
+// `prefetched` (nullable): registers a caller is loading during this step (the rollout's next action).  They are
+// consumed here, right after the IK and BEFORE this step's stores are issued: the s_waitcnt the consumption needs
+// then covers only that old load; placed at the next step's top it would also wait for this step's stores
+// (vmcnt is in-order) -- measured 15 % of the wave's cycles.
+template <bool CARRY = false, int PEEL = 0, class L, typename T>
+AE_DEV int lane_env_step(L &l, const EnvParams<T> &P, int64_t i, const T (&a)[3], const StepIO &io, ActionPrefetch *prefetched = nullptr,
+                         float (*next_action)[3] = nullptr) {
+  using C = typename L::Chain;
+  T tgt[3];
+  l.template step_begin<CARRY>(P, a, tgt);
+  const int updates = ik_lockstep<C, T, L::kMode, PEEL>(P.chain, P.ik, l.q, tgt, l.S, l.cq, l.sq, l.minpiv);
+  const bool lim_hit = ik_limits<C, T, L::kMode>(P.chain, P.ik, l.q, l.S, l.cq, l.sq);
+  if (prefetched) prefetch_settle(*prefetched, *next_action);
+  l.template step_tail<CARRY>(P, i, io, updates, lim_hit);
+  return updates;
+}
+
 // Per-lane state of one reach env and the body of one env step.  The single-step kernel and the T-step rollout
 // kernel both run this code: a rollout of any length is bit-identical to the same steps as separate launches (see `cq` below).
 template <class C, typename T, int MODE = 0> struct ReachLane {
@@ -402,16 +454,14 @@ template <class C, typename T, int MODE = 0> struct ReachLane {
   // that is also the frame the NEXT step starts from, so a kernel that keeps the lane in registers across steps (CARRY: the
   // rollout kernels without a fused actor) carries it over instead of recomputing it from the same (cos q, sin q): 120 of a
   // step's ~3 300 instructions, the same bits.  Since round 4 the frame is made EAGERLY wherever the pose is set anew -- at the
-  // launch's start (make_frame), inside the in-place reset and the trig re-derivation (both rare, out of line) -- so that
+  // launch's start (lane_make_frame), inside the in-place reset and the trig re-derivation (both rare, out of line) -- so that
   // step_begin tests nothing: the lazy "if (!have_S) fk" of rounds 1-3 was a taken branch on every step.
   FKState<T> S;
-  AE_DEV void make_frame(const EnvParams<T> &P) { fk<C, T>(P.chain, cq, sq, S); }
   float g[3];
   int32_t step;
   T ep_ret;
-  uint32_t n_done = 0, n_succ = 0, n_bad = 0, n_upd = 0;   // flushed to the handle's counters once per launch
-  uint32_t n_lim = 0, n_low = 0, n_cap = 0, n_cond = 0;    // parity fence: steps the IK left the URDF limits / ended with the flange below fence_z / ran to the iteration cap / was ill-conditioned
-  T minpiv = T(1e30);                                      // smallest LDL^T pivot of the running step's IK call (fence bookkeeping)
+  LaneCounts cnt;          // flushed to the handle's counters once per launch
+  T minpiv = T(1e30);      // smallest LDL^T pivot of the running step's IK call (fence bookkeeping)
 
   AE_DEV void load(const EnvParams<T> &P, int64_t i) {
     const int64_t n = P.n;
@@ -421,7 +471,6 @@ template <class C, typename T, int MODE = 0> struct ReachLane {
     ep_ret = P.ep_return[i];
     static_for<0, NJ>([&](auto JI) { constexpr int j = JI; cq[j] = P.trig[(int64_t)j * n + i]; sq[j] = P.trig[(int64_t)(NJ + j) * n + i]; });
   }
-  AE_DEV void derive_trig() { sincos_all<T>(q, cq, sq); }
 
   AE_DEV void store(const EnvParams<T> &P, int64_t i) {
     const int64_t n = P.n;
@@ -429,11 +478,11 @@ template <class C, typename T, int MODE = 0> struct ReachLane {
     static_for<0, NJ>([&](auto JI) { constexpr int j = JI; P.trig[(int64_t)j * n + i] = cq[j]; P.trig[(int64_t)(NJ + j) * n + i] = sq[j]; });
     P.step[i] = step;
     P.ep_return[i] = ep_ret;
-    flush_counts(P, i, n_done, n_succ, n_bad, n_upd, n_lim, n_low, n_cap, n_cond);
+    flush_counts(P, cnt);
   }
 
   // RLReachEnv.step + _reward (rl_reach_env.py:219-319) in three pieces -- step_begin, the IK trips (ik_trip), step_tail --
-  // so that the lockstep kernels (env_step below: all lanes of a wave walk through a step together) and the
+  // so that the lockstep kernels (lane_env_step above: all lanes of a wave walk through a step together) and the
   // lane-asynchronous rollout kernel (env_rollout_async_kernel: every lane at its own step and trip) run the same code.
   //
   // step_begin: everything ahead of the IK trips -- the frame of the start pose (carried over or recomputed) and the
@@ -441,7 +490,7 @@ template <class C, typename T, int MODE = 0> struct ReachLane {
   // CARRY: S already is the frame of (cq, sq) (see S above); otherwise it is computed here.
   template <bool CARRY>
   AE_DEV void step_begin(const EnvParams<T> &P, const T (&a)[3], T (&tgt)[3]) {
-    if constexpr (!CARRY) make_frame(P);
+    if constexpr (!CARRY) lane_make_frame(*this, P);
     ik_target<T, false>(S, a, P.dv, P.box_lo, P.box_hi, tgt);
     minpiv = T(1e30);
   }
@@ -451,15 +500,7 @@ template <class C, typename T, int MODE = 0> struct ReachLane {
   template <bool CARRY>
   AE_DEV void step_tail(const EnvParams<T> &P, int64_t i, const StepIO &io, int updates, bool lim_hit) {
     const int64_t n = P.n;
-    n_upd += (uint32_t)updates;
-    if constexpr (kFence) {
-      n_lim += lim_hit ? 1u : 0u; n_low += (S.p[2] < P.fence_z) ? 1u : 0u; n_cap += (updates >= P.ik.max_iters) ? 1u : 0u;
-      n_cond += (minpiv < P.ik.fence_pivot) ? 1u : 0u;
-      // the per-step view of the update / cap counts.  Only in the bookkeeping builds: as a nullable pointer of the default
-      // kernels it stayed live in two scalar registers across the IK loop, whose f64 constants were then rematerialised on
-      // every trip (+7 scalar instructions per trip, +1.3 % on the headline; A/B against the round-2 tree)
-      if (io.updates) io.updates[i] = (uint8_t)(updates > 255 ? 255 : updates);
-    }
+    lane_count_ik(*this, P, i, io, updates, lim_hit);
     step += 1;                                                                    // :264
     const T dx = S.p[0] - (T)g[0], dy = S.p[1] - (T)g[1], dz = S.p[2] - (T)g[2];
     const T dist = M::sqrt(M::fma(dx, dx, M::fma(dy, dy, dz * dz)));              // :281
@@ -480,7 +521,7 @@ template <class C, typename T, int MODE = 0> struct ReachLane {
       const T sum = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + q[6]);
       finite = M::finite(sum);
     }
-    if (!finite) n_bad += 1;
+    if (!finite) cnt.bad += 1;
 
     io.reward[i] = (float)reward;
     io.done[i] = done ? 1 : 0;
@@ -498,8 +539,8 @@ template <class C, typename T, int MODE = 0> struct ReachLane {
         P.last_return[i] = ep_ret;
         P.last_len[i] = step;
         P.last_success[i] = succ ? 1 : 0;
-        n_done += 1;
-        if (succ) n_succ += 1;
+        cnt.done += 1;
+        if (succ) cnt.succ += 1;
       }
       if (done && P.auto_reset) {
         const uint32_t ep = P.episode[i];
@@ -513,37 +554,15 @@ template <class C, typename T, int MODE = 0> struct ReachLane {
         ep_ret = T(0);
         store_obs6<T>(io.obs, i, K.p_init, g);      // the same lane's second store to these addresses: program order holds
         cur_obs[0] = (float)K.p_init[0]; cur_obs[1] = (float)K.p_init[1]; cur_obs[2] = (float)K.p_init[2];
-        if constexpr (CARRY) make_frame(P);
+        if constexpr (CARRY) lane_make_frame(*this, P);
       } else if (rederive) {
-        derive_trig();
-        if constexpr (CARRY) make_frame(P);
+        sincos_all<T>(q, cq, sq);
+        if constexpr (CARRY) lane_make_frame(*this, P);
       }
     }
   }
-  // The lockstep step.  Returns the number of IK updates.
-  // `prefetched` (nullable): registers a caller is loading during this step (the rollout's next action).  They are
-  // consumed here, right after the IK and BEFORE this step's stores are issued: the s_waitcnt the consumption needs
-  // then covers only that old load; placed at the next step's top it would also wait for this step's stores
-  // (vmcnt is in-order) -- measured 15 % of the wave's cycles.
-  template <bool CARRY = false, int PEEL = 0>
-  AE_DEV int env_step(const EnvParams<T> &P, int64_t i, const T (&a)[3], const StepIO &io, ActionPrefetch *prefetched = nullptr,
-                    float (*next_action)[3] = nullptr) {
-    T tgt[3];
-    step_begin<CARRY>(P, a, tgt);
-    const int updates = ik_lockstep<C, T, kMode, PEEL>(P.chain, P.ik, q, tgt, S, cq, sq, minpiv);                               // :244-257
-    const bool lim_hit = ik_limits<C, T, kMode>(P.chain, P.ik, q, S, cq, sq);
-    if (prefetched) prefetch_settle(*prefetched, *next_action);
-    step_tail<CARRY>(P, i, io, updates, lim_hit);
-    return updates;
-  }
 
   float cur_obs[3];   // eef part of the observation the policy sees next (goal part is g)
-  // eef of the current state, for the first policy call of a launch (later ones reuse the step's exit FK)
-  AE_DEV void refresh_obs(const EnvParams<T> &P) {
-    FKState<T> F;
-    fk<C, T>(P.chain, cq, sq, F);
-    cur_obs[0] = (float)F.p[0]; cur_obs[1] = (float)F.p[1]; cur_obs[2] = (float)F.p[2];
-  }
   AE_DEV void policy_obs(float (&s)[6]) const {
     s[0] = cur_obs[0]; s[1] = cur_obs[1]; s[2] = cur_obs[2]; s[3] = g[0]; s[4] = g[1]; s[5] = g[2];
   }
@@ -609,19 +628,13 @@ template <class C, typename T, bool PICK, int MODE = 0> struct CubeLane {
   T cube[3], target[3], d_last;
   T vel[2] = {T(0), T(0)};  // push: the cube's planar velocity (push_contact_model 1)
   FKState<T> S;             // link frames of the current pose, carried from step to step (push only): see ReachLane::S
-  AE_DEV void make_frame(const EnvParams<T> &P) { fk<C, T>(P.chain, cq, sq, S); }
   T grip = T(0);            // pick: 0 open, 1 closed, 2 closed and holding the cube
   T off[3] = {T(0), T(0), T(0)};   // pick: cube - tip while held
   int32_t step;
   T ep_ret;
-  uint32_t n_done = 0, n_succ = 0, n_bad = 0, n_upd = 0, n_lim = 0, n_low = 0, n_cap = 0, n_cond = 0;
+  LaneCounts cnt;
   T minpiv = T(1e30);       // smallest LDL^T pivot of the running step's IK call (fence bookkeeping)
   float cur_obs[3];
-  AE_DEV void refresh_obs(const EnvParams<T> &P) {
-    FKState<T> F;
-    fk<C, T>(P.chain, cq, sq, F);
-    cur_obs[0] = (float)F.p[0]; cur_obs[1] = (float)F.p[1]; cur_obs[2] = (float)F.p[2];
-  }
   AE_DEV void policy_obs(float (&s)[9]) const {
     static_for<0, 3>([&](auto KI) { constexpr int k = KI; s[k] = cur_obs[k]; s[3 + k] = (float)cube[k]; s[6 + k] = (float)target[k]; });
   }
@@ -678,7 +691,6 @@ template <class C, typename T, bool PICK, int MODE = 0> struct CubeLane {
     ep_ret = P.ep_return[i];
     static_for<0, NJ>([&](auto JI) { constexpr int j = JI; cq[j] = P.trig[(int64_t)j * n + i]; sq[j] = P.trig[(int64_t)(NJ + j) * n + i]; });
   }
-  AE_DEV void derive_trig() { sincos_all<T>(q, cq, sq); }
 
   AE_DEV void store(const EnvParams<T> &P, int64_t i) {
     const int64_t n = P.n;
@@ -694,7 +706,7 @@ template <class C, typename T, bool PICK, int MODE = 0> struct CubeLane {
     }
     P.step[i] = step;
     P.ep_return[i] = ep_ret;
-    flush_counts(P, i, n_done, n_succ, n_bad, n_upd, n_lim, n_low, n_cap, n_cond);
+    flush_counts(P, cnt);
   }
 
   // stepSimulation (:349), simplified: sphere (tool, radius r, centre p) vs axis-aligned box (cube, half-size h)
@@ -827,7 +839,7 @@ template <class C, typename T, bool PICK, int MODE = 0> struct CubeLane {
   template <bool CARRY>
   AE_DEV void step_begin(const EnvParams<T> &P, const T (&a)[3], T (&tgt)[3]) {
     if constexpr (PICK) { q7s = q[NJ - 1]; c7s = cq[NJ - 1]; s7s = sq[NJ - 1]; }
-    if constexpr (!(CARRY && !PICK)) make_frame(P);
+    if constexpr (!(CARRY && !PICK)) lane_make_frame(*this, P);
     p0[0] = S.p[0]; p0[1] = S.p[1]; p0[2] = S.p[2];
     ik_target<T, PICK>(S, a, P.dv, P.box_lo, P.box_hi, tgt);
     minpiv = T(1e30);
@@ -835,15 +847,7 @@ template <class C, typename T, bool PICK, int MODE = 0> struct CubeLane {
   template <bool CARRY>
   AE_DEV void step_tail(const EnvParams<T> &P, int64_t i, const StepIO &io, int updates, bool lim_hit) {
     constexpr bool kCarry = CARRY && !PICK;
-    n_upd += (uint32_t)updates;
-    if constexpr (kFence) {
-      n_lim += lim_hit ? 1u : 0u; n_low += (S.p[2] < P.fence_z) ? 1u : 0u; n_cap += (updates >= P.ik.max_iters) ? 1u : 0u;
-      n_cond += (minpiv < P.ik.fence_pivot) ? 1u : 0u;
-      // the per-step view of the update / cap counts.  Only in the bookkeeping builds: as a nullable pointer of the default
-      // kernels it stayed live in two scalar registers across the IK loop, whose f64 constants were then rematerialised on
-      // every trip (+7 scalar instructions per trip, +1.3 % on the headline; A/B against the round-2 tree)
-      if (io.updates) io.updates[i] = (uint8_t)(updates > 255 ? 255 : updates);
-    }
+    lane_count_ik(*this, P, i, io, updates, lim_hit);
     if constexpr (PICK) {
       q[NJ - 1] = q7s;              // rl_pick_env.py:343: joints 0..5 only; link-7 position and tool axis do not depend on q7
       cq[NJ - 1] = c7s; sq[NJ - 1] = s7s;
@@ -891,7 +895,7 @@ template <class C, typename T, bool PICK, int MODE = 0> struct CubeLane {
       const T sum = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + q[6]);
       finite = M::finite(sum);
     }
-    if (!finite) n_bad += 1;
+    if (!finite) cnt.bad += 1;
 
     io.reward[i] = (float)reward;
     io.done[i] = done ? 1 : 0;
@@ -906,8 +910,8 @@ template <class C, typename T, bool PICK, int MODE = 0> struct CubeLane {
         P.last_return[i] = ep_ret;
         P.last_len[i] = step;
         P.last_success[i] = succ ? 1 : 0;
-        n_done += 1;
-        if (succ) n_succ += 1;
+        cnt.done += 1;
+        if (succ) cnt.succ += 1;
       }
       if (done && P.auto_reset) {
         const uint32_t ep = P.episode[i];
@@ -923,23 +927,12 @@ template <class C, typename T, bool PICK, int MODE = 0> struct CubeLane {
         ep_ret = T(0);
         store_obs9<T>(io.obs, i, K.p_init, cube, target);      // the same lane's second store to these addresses
         cur_obs[0] = (float)K.p_init[0]; cur_obs[1] = (float)K.p_init[1]; cur_obs[2] = (float)K.p_init[2];
-        if constexpr (kCarry) make_frame(P);
+        if constexpr (kCarry) lane_make_frame(*this, P);
       } else if (rederive) {
-        derive_trig();
-        if constexpr (kCarry) make_frame(P);
+        sincos_all<T>(q, cq, sq);
+        if constexpr (kCarry) lane_make_frame(*this, P);
       }
     }
-  }
-  template <bool CARRY = false, int PEEL = 0>
-  AE_DEV int env_step(const EnvParams<T> &P, int64_t i, const T (&a)[3], const StepIO &io, ActionPrefetch *prefetched = nullptr,
-                    float (*next_action)[3] = nullptr) {
-    T tgt[3];
-    step_begin<CARRY>(P, a, tgt);
-    const int updates = ik_lockstep<C, T, kMode, PEEL>(P.chain, P.ik, q, tgt, S, cq, sq, minpiv);                               // :339-347
-    const bool lim_hit = ik_limits<C, T, kMode>(P.chain, P.ik, q, S, cq, sq);
-    if (prefetched) prefetch_settle(*prefetched, *next_action);
-    step_tail<CARRY>(P, i, io, updates, lim_hit);
-    return updates;
   }
 };
 template <class C, typename T, int MODE = 0> using PushLane = CubeLane<C, T, false, MODE>;
@@ -975,7 +968,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
   TL_STAMP(tl1);
-  const int updates = L.template env_step<false, ARMENV_STEP_PEEL>(P, i, a, io);
+  const int updates = lane_env_step<false, ARMENV_STEP_PEEL>(L, P, i, a, io);
   (void)updates;
   TL_STAMP(tl2);
   L.store(P, i);
@@ -985,7 +978,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
     TL_STAMP(tl3);
     int mx = updates;
     for (int o = 32; o; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
-    const unsigned long long dn = __ballot(L.n_done != 0);
+    const unsigned long long dn = __ballot(L.cnt.done != 0);
     if ((threadIdx.x & 63) == 0 && g_timeline) {
       unsigned long long *r = g_timeline + 8 * ((int64_t)(tl_launch & 15) * (P.n >> 6) + (i >> 6));
       unsigned xcc, hw;
@@ -1049,7 +1042,7 @@ void env_rollout_kernel(EnvParams<T> P, PolicyParams pol, int32_t steps, const f
   Lane L;
   L.load(P, i);
   uint32_t episode = (POLICY != ARMENV_POLICY_EXTERNAL) ? P.episode[i] : 0u;
-  if constexpr (kActor) L.refresh_obs(P);
+  if constexpr (kActor) lane_refresh_obs(L, P);
   float an[3] = {0.f, 0.f, 0.f};
   if constexpr (kPrefetch) {
     an[0] = actions[3 * i]; an[1] = actions[3 * i + 1]; an[2] = actions[3 * i + 2];
@@ -1065,12 +1058,12 @@ void env_rollout_kernel(EnvParams<T> P, PolicyParams pol, int32_t steps, const f
   constexpr bool kCarry = !kActor;
   // straight-line IK trips ahead of the trip loop (armenv_kin.h ik_lockstep); none beside a fused actor (register pressure)
   constexpr int kPeel = kActor ? 0 : ARMENV_ROLLOUT_PEEL;
-  if constexpr (kCarry) L.make_frame(P);
+  if constexpr (kCarry) lane_make_frame(L, P);
   for (int32_t t = 0; t < steps; ++t) {
     T a[3];
     if constexpr (kPrefetch) {
       a[0] = (T)an[0]; a[1] = (T)an[1]; a[2] = (T)an[2];
-      // prefetch the next step's action (the last step re-reads its own); settled inside env_step, after the IK
+      // prefetch the next step's action (the last step re-reads its own); settled inside lane_env_step, after the IK
       prefetch_issue(actions + ((int64_t)(t + 1 < steps ? t + 1 : t) * n + i) * 3, an_next);
     } else if constexpr (POLICY == ARMENV_POLICY_EXTERNAL) {
       const float *ap = actions + ((int64_t)t * n + i) * 3;
@@ -1116,17 +1109,17 @@ void env_rollout_kernel(EnvParams<T> P, PolicyParams pol, int32_t steps, const f
       if constexpr (POLICY == ARMENV_POLICY_EXTERNAL) { ao[0] = (float)a[0]; ao[1] = (float)a[1]; ao[2] = (float)a[2]; }
       else { ao[0] = an[0]; ao[1] = an[1]; ao[2] = an[2]; }
     }
-    const uint32_t before = L.n_done;
+    const uint32_t before = L.cnt.done;
     int upd;
     if constexpr (kPrefetch) {
-      upd = L.template env_step<kCarry, kPeel>(P, i, a, io, &an_next, &an);
+      upd = lane_env_step<kCarry, kPeel>(L, P, i, a, io, &an_next, &an);
     } else {
-      upd = L.template env_step<kCarry, kPeel>(P, i, a, io);
+      upd = lane_env_step<kCarry, kPeel>(L, P, i, a, io);
     }
     if constexpr (Lane::kFence) w_trips += wave_max8((uint32_t)upd + 1u);   // a lane's trips: its updates + the exit trip
     else (void)upd;
     if constexpr (POLICY != ARMENV_POLICY_EXTERNAL) {
-      if (L.n_done != before && P.auto_reset) episode += 1u;
+      if (L.cnt.done != before && P.auto_reset) episode += 1u;
     }
   }
   L.store(P, i);
@@ -1147,7 +1140,7 @@ void env_rollout_kernel(EnvParams<T> P, PolicyParams pol, int32_t steps, const f
 // the wave pays ~max_lane sum_t trips (pick 6.5, push 4.4) plus one tail block per transition round.  ready_lanes trades
 // the two: 64 is lockstep (one tail per step), 1 runs a tail block on nearly every trip.  `straggler_trips` > 0 replaces the
 // count by a rule that knows what the slow lanes are (ArmEnvConfig.rollout_straggler_trips; tests/tools/async_policy_sim.py).
-// Per-lane arithmetic, its order and every store are those of env_step: trajectories are bit-identical to the lockstep
+// Per-lane arithmetic, its order and every store are those of lane_env_step: trajectories are bit-identical to the lockstep
 // kernels and to armenv_step launches (tested).  Not used with the fused actors (their MFMA phases are wave-synchronous).
 // WAVES: register budget as for env_rollout_kernel (2: <= 256 registers per lane, for batches with more waves than SIMDs).
 template <class Lane, typename T, int POLICY, int WAVES = 1>
@@ -1199,7 +1192,7 @@ void env_rollout_async_kernel(EnvParams<T> P, PolicyParams pol, int32_t steps, c
     ready = false;
   };
   load_action(0);
-  L.make_frame(P);          // carried from step to step in registers from here on (ReachLane::S; pick recomputes it per step)
+  lane_make_frame(L, P);    // carried from step to step in registers from here on (ReachLane::S; pick recomputes it per step)
   begin_step();
   [[maybe_unused]] uint32_t w_trips = 0, w_rounds = 0;
   for (;;) {
@@ -1225,11 +1218,11 @@ void env_rollout_async_kernel(EnvParams<T> P, PolicyParams pol, int32_t steps, c
         io.success = io0.success + (int64_t)t * n;
         io.terminal_obs = io0.terminal_obs ? io0.terminal_obs + (int64_t)t * n * kObs : nullptr;
         if constexpr (Lane::kFence) io.updates = io0.updates ? io0.updates + (int64_t)t * n : nullptr; else io.updates = nullptr;
-    if constexpr (kTipOf(Lane::kMode)) io.diag = io0.diag ? io0.diag + (int64_t)t * n * 4 : nullptr; else io.diag = nullptr;
-        const uint32_t before = L.n_done;
+        if constexpr (kTipOf(Lane::kMode)) io.diag = io0.diag ? io0.diag + (int64_t)t * n * 4 : nullptr; else io.diag = nullptr;
+        const uint32_t before = L.cnt.done;
         L.template step_tail<true>(P, i, io, updates, lim_hit);
         if constexpr (POLICY != ARMENV_POLICY_EXTERNAL) {
-          if (L.n_done != before && P.auto_reset) episode += 1u;
+          if (L.cnt.done != before && P.auto_reset) episode += 1u;
         }
         ready = false;
         ++t;
