@@ -71,6 +71,10 @@ class ArmEnvHerPopArgs(C.Structure):
     _fields_ = [("one", ArmEnvHerArgs), ("members", C.c_int32), ("episodes_stride", C.c_int64)]
 
 
+class ArmEnvHerPopSharedArgs(C.Structure):
+    _fields_ = [("pop", ArmEnvHerPopArgs), ("share_ratio", C.c_double)]
+
+
 class ArmEnvMlpRW(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("W1", "b1", "W2", "b2", "W3", "b3")]
 
@@ -171,6 +175,7 @@ SYMBOLS = {
     "armenv_write_episodes": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, _P, _P]),
     "armenv_her_sample": (C.c_int, [C.c_int32, C.POINTER(ArmEnvHerArgs), _P]),
     "armenv_her_pop_sample": (C.c_int, [C.c_int32, C.POINTER(ArmEnvHerPopArgs), _P]),
+    "armenv_her_pop_sample_shared": (C.c_int, [C.c_int32, C.POINTER(ArmEnvHerPopSharedArgs), _P]),
     "armenv_pop_count_episodes": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P]),
     "armenv_pop_write_episodes": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, _P,
                                             C.c_int64, _P]),

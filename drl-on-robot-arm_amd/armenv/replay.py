@@ -8,6 +8,7 @@ in front, so the time axis of a ring is ``len(_lead)``.  Two thin classes set ``
 
   TrajectoryStore             _lead = ()     armenv_count_episodes / armenv_write_episodes / armenv_her_sample
   PopulationTrajectoryStore   _lead = (P,)   armenv_pop_count_episodes / armenv_pop_write_episodes / armenv_her_pop_sample
+                                             (``sample(share_ratio=...)`` other than 0: armenv_her_pop_sample_shared)
 
 The population store (armenv.train_pop) indexes and samples all P members in one launch each.  The single store keeps its own entry
 points and kernels: they are what the population kernels are proven against, bit for bit."""
@@ -77,7 +78,7 @@ class _Store:
         self._lib = L.load()
         self._draw = 0
         self._ring = None
-        self._bound = None             # (key, out, ArmEnvHerPopArgs) of the last ``sample``; dropped whenever the ring or its index moves
+        self._bound = None             # (key, out, argument struct) of the last ``sample``; dropped whenever the ring or its index moves
         self._started = False          # the first append has stored obs0
 
     @property
@@ -235,32 +236,41 @@ class _Store:
         ``picks`` i32 ``_lead`` + [B][4]: teacher-forced draws.  ``return_picks``: ``out["picks"]`` i32 ``_lead`` + [B][4]; a tensor
         of that kind already in ``out`` is written in place, by both stores.  The argument struct is built once per (``out``,
         settings, state of the ring); later calls only refresh `draw` and the two picks pointers."""
+        return self._sample(batch_size, use_her, dis_threshold, her_ratio, picks, return_picks, out)
+
+    def _sample(self, batch_size, use_her, dis_threshold, her_ratio, picks, return_picks, out, share_ratio=0.0):
+        """``sample``'s body.  ``share_ratio`` (the population store's, see its ``sample``): 0.0 is ``sample`` as it stands; any other
+        value goes through ``_launch_shared`` with the struct wrapped in an ArmEnvHerPopSharedArgs, and the picks are 5 wide, the
+        source member in front."""
         if self._ring is None:
             raise RuntimeError("%s.sample: no rollout stored" % type(self).__name__)
-        lead, B, dev = self._lead, int(batch_size), self.device
+        lead, B, dev, share = self._lead, int(batch_size), self.device, float(share_ratio)
+        width = 5 if share else 4                                 # of a pick
         if out is None:
             out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in self._batch_spec(B).items()}
-        key = (B, bool(use_her), float(dis_threshold), float(her_ratio)) + tuple(out[k].data_ptr() for k in _BATCH_KEYS)
+        key = (B, bool(use_her), float(dis_threshold), float(her_ratio), share) + tuple(out[k].data_ptr() for k in _BATCH_KEYS)
         bound = self._bound
         if bound is not None and bound[0] == key and bound[1] is out:
             args = bound[2]
         else:
             args = self._bind(B, use_her, dis_threshold, her_ratio, out)
+            if share:
+                args = L.ArmEnvHerPopSharedArgs(args, share)
             self._bound = (key, out, args)                        # holds `out`: the pointers in `args` stay valid
-        a = args.one
+        a = args.pop.one if share else args.one
         pk = None
         if picks is not None:
             pk = torch.as_tensor(picks).to(device=dev, dtype=torch.int32).contiguous()
-            assert tuple(pk.shape) == lead + (B, 4)
+            assert tuple(pk.shape) == lead + (B, width)
         a.picks_dev = None if pk is None else pk.data_ptr()
         if return_picks:
             t = out.get("picks")
-            if t is None or tuple(t.shape) != lead + (B, 4) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
-                out["picks"] = torch.empty(lead + (B, 4), dtype=torch.int32, device=dev)
+            if t is None or tuple(t.shape) != lead + (B, width) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                out["picks"] = torch.empty(lead + (B, width), dtype=torch.int32, device=dev)
         a.picks_out_dev = out["picks"].data_ptr() if return_picks else None
         a.draw = self._draw
         self._draw += 1
-        L.check(self._launch(dev.index or 0, args, self._stream()))
+        L.check((self._launch_shared if share else self._launch)(dev.index or 0, args, self._stream()))
         if pk is not None:
             torch.cuda.current_stream(dev).synchronize()
         return out
@@ -356,6 +366,22 @@ class PopulationTrajectoryStore(_Store):
 
     def _launch(self, dev, args, stream):
         return self._lib.armenv_her_pop_sample(dev, C.byref(args), stream)
+
+    def _launch_shared(self, dev, args, stream):
+        return self._lib.armenv_her_pop_sample_shared(dev, C.byref(args), stream)
+
+    def sample(self, batch_size, use_her=True, dis_threshold=0.1, her_ratio=0.8, picks=None, return_picks=False, out=None,
+               share_ratio=0.0):
+        """``_Store.sample`` for every member in one launch.  ``share_ratio`` in [0, 1]: the probability that a row of a member's
+        batch is drawn from the trajectories of ALL members (a shared replay buffer: uniform over the union of their episodes)
+        and not from its own; the draw rule is armenv_her_pop_sample_shared's in include/armenv.h.  0.0 (the default) is the call
+        without the argument: the same entry point, bytes and picks [P][B][4].  Any other value: ``picks`` and ``out["picks"]``
+        are [P][B][5] = (source member, episode within it, step_state, use_her, step_goal).  The draw counter advances by one
+        either way.  ValueError for a value outside [0, 1] or NaN, before any device call."""
+        share = float(share_ratio)
+        if not 0.0 <= share <= 1.0:
+            raise ValueError("PopulationTrajectoryStore.sample: share_ratio must be in [0, 1], not %r" % (share_ratio,))
+        return self._sample(batch_size, use_her, dis_threshold, her_ratio, picks, return_picks, out, share)
 
     def rollout_buffers(self, steps, N, D):
         """P dicts, member p's being contiguous views [steps][N][...] into one stacked staging block [P][steps][N][...], under the

@@ -9,6 +9,7 @@ update is one ``train`` = two reference updates on the batch, as in armenv.train
     python -m armenv.train_pop --members 16 --iterations 200 --algo daddpg
     python -m armenv.train_pop --members 4 --sweep actor_lr=1e-3,5e-4,2e-4,1e-4 --sweep tau=0.005,0.005,0.01,0.01
     python -m armenv.train_pop --members 8 --iterations 60 --pbt-every 10
+    python -m armenv.train_pop --members 8 --iterations 100 --share-replay 0.5
 
 ``sweep`` (``--sweep NAME=v0,v1,...``, one value per member): the members' own values of the agent's sweepable hyper-parameters
 (``sweepable_names(algo)``: the learning rates, tau, gamma, the target-policy noise's two, DARC's two weights) and of ``expl_sigma``,
@@ -19,6 +20,11 @@ every N iterations the members are ranked by their success rate since the last s
 members of the top (``pop.exploit``: nets, targets, moments and hyper-parameters, ONE launch) and their hyper-parameters -- and
 ``expl_sigma`` -- are perturbed (``explore``).  A replaced member keeps its environments, its replay ring and its noise seed.  Each
 step is logged and kept in the history as a ``kind="pbt"`` record; every record then carries the members' current values.
+
+``share_ratio`` (``--share-replay F``, F in [0, 1], ``store="population"`` only): a shared replay buffer.  Every row of a member's
+batch is drawn, with probability F, from the trajectories of ALL members -- uniformly over the union of their episodes -- and from
+its own otherwise (``PopulationTrajectoryStore.sample(share_ratio=F)``: still one launch per batch).  A member replaced by a PBT
+step then no longer learns from the discarded policy's data alone.  0 (the default): the loop and its launches as without it.
 
 Member p has its own environments, trajectory store, initial weights and noise, all seeded ``seed + p``.  Rollouts are P launches,
 one per member, each with that member's policy (TD3: its actor; the two-actor agents: their own take_action, fused into the rollout
@@ -89,7 +95,8 @@ def _checked_pbt(pbt, algo, members, seed=0):
 def train_reach_population(members=16, num_envs=64, iterations=200, rollout_steps=32, updates=40, batch_size=256, her_ratio=0.8,
                            seed=0, device="cuda:0", actor_kind="actor_f16x3", expl_sigma=None, log_every=10, log=print,
                            window_steps=1536, minimal_episodes=5, max_steps=500, task="reach", algo="td3", store="population",
-                           sweep=None, pbt=None, checkpoint=None, checkpoint_every=0, resume=None, save=None, save_best=False):
+                           sweep=None, pbt=None, checkpoint=None, checkpoint_every=0, resume=None, save=None, save_best=False,
+                           share_ratio=0.0):
     """Returns (population, history); a history record holds the members' success rates over the last ``log_every`` iterations.
     ``task="push" | "pick"``: armenv.train.train_push's settings (state_dim 9, action_bound 0.4, unclipped exploration noise).
     ``algo``: the agent; the two-actor agents explore as armenv.train has them explore on that task (the same sigma and clip).
@@ -101,6 +108,8 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
     the device.  The history then also holds one ``kind="pbt"`` record per PBT step -- iteration, the fitness (success rates since
     the last step), ``src`` and the replaced members' new values -- and every record holds the members' current values as
     ``hyper``.  Without it the loop, the records and the trained bits are what they are without the argument.
+    ``share_ratio``: the module's docstring; in [0, 1], and 0 with ``store="members"``, or ValueError before anything is created on
+    the device.  It is part of the run's configuration: a resume with another value is refused.
     ``checkpoint``, ``checkpoint_every``, ``resume``, ``save``, ``save_best``: the module's docstring; a `resume` whose saved arguments
     are not this call's raises ValueError naming the first that differs, before anything is created on the device."""
     if task not in _TASKS:
@@ -109,6 +118,11 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
         raise ValueError("algo must be one of %s" % ", ".join(ALGOS))
     if store not in STORES:
         raise ValueError("store must be one of %s" % ", ".join(STORES))
+    share_ratio = float(share_ratio)
+    if not 0.0 <= share_ratio <= 1.0:
+        raise ValueError("share_ratio must be in [0, 1], not %r" % share_ratio)
+    if share_ratio and store != "population":
+        raise ValueError('share_ratio = %r needs store="population": the members\' own stores cannot read each other' % share_ratio)
     Env, state_dim, action_bound = _TASKS[task]
     sigma = expl_sigma if expl_sigma is not None else action_bound * 0.98
     noise_clip = action_bound if task == "reach" else 1e9
@@ -121,6 +135,8 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
                   batch_size=batch_size, her_ratio=her_ratio, seed=seed, actor_kind=actor_kind, expl_sigma=sigma, window_steps=window_steps,
                   minimal_episodes=minimal_episodes, max_steps=max_steps, store=store, sweep=sweep,
                   pbt=None if pbt is None else {k: v for k, v in pbt.state_dict().items() if k != "rng"})
+    if share_ratio:                # recorded where it is used: a run without it writes, and resumes from, the checkpoints it always did
+        config["share_ratio"] = share_ratio
     saved = None
     if resume is not None:
         saved = load_run(resume)
@@ -183,7 +199,7 @@ def train_reach_population(members=16, num_envs=64, iterations=200, rollout_step
             # lockstep: re-checked every iteration (a ring window can lose its complete episodes again, see armenv.train)
             if pstore.ready(minimal_episodes):
                 for _ in range(updates):
-                    pstore.sample(batch_size, use_her=True, her_ratio=her_ratio, out=batch)
+                    pstore.sample(batch_size, use_her=True, her_ratio=her_ratio, out=batch, share_ratio=share_ratio)
                     pop.train(batch)                      # datd3 / darc: two updates, as the reference's run() counts them
         else:
             for p, e in enumerate(es):
@@ -264,9 +280,13 @@ def main():
                          "their hyper-parameters")
     ap.add_argument("--pbt-fraction", type=float, default=0.25, metavar="F", help="the bottom's (and the top's) share of the members, in (0, 0.5]")
     ap.add_argument("--pbt-perturb", default="0.8,1.2", metavar="LO,HI", help="the two factors a perturbed value is multiplied by")
+    ap.add_argument("--share-replay", type=float, default=0.0, metavar="F",
+                    help="the share, in [0, 1], of every member's batch that is drawn from all members' trajectories (--store population)")
     add_cli_arguments(ap)
     a = ap.parse_args()
     check_cli_arguments(ap, a, "fused")
+    if not 0.0 <= a.share_replay <= 1.0 or (a.share_replay and a.store != "population"):
+        ap.error("--share-replay: a number in [0, 1], and 0 unless --store population")
     pbt = None
     if a.pbt_every is not None:
         try:
@@ -288,7 +308,7 @@ def main():
     train_reach_population(a.members, a.num_envs, a.iterations, a.rollout_steps, a.updates, a.batch_size, seed=a.seed,
                            actor_kind=a.actor, window_steps=a.window_steps, max_steps=a.max_steps, task=a.task, algo=a.algo, store=a.store,
                            sweep=sweep or None, pbt=pbt, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every, resume=a.resume,
-                           save=a.save, save_best=a.save_best)
+                           save=a.save, save_best=a.save_best, share_ratio=a.share_replay)
 
 
 if __name__ == "__main__":

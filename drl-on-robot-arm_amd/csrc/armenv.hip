@@ -617,7 +617,7 @@ static HerArgs her_args(const ArmEnvHerArgs *a) {
 
 extern "C" {
 
-// ---- the trajectory store.  All six entry points refuse a bad argument by its name before the first HIP call, return ARMENV_OK
+// ---- the trajectory store.  All seven entry points refuse a bad argument by its name before the first HIP call, return ARMENV_OK
 // without a launch for an empty batch, then launch their own kernel form.  One set of checks: the single forms are members = 1.
 #define STORE_REFUSE(why) \
   if (const char *why_ = (why)) return fail(ARMENV_EINVAL, "%s: %s", __func__, why_)
@@ -727,6 +727,24 @@ int armenv_her_pop_sample(int32_t device, const ArmEnvHerPopArgs *args, void *st
     hipLaunchKernelGGL((her_sample_pop_kernel<6>), grid, block, 0, static_cast<hipStream_t>(stream), h, args->members, args->episodes_stride);
   else
     hipLaunchKernelGGL((her_sample_pop_kernel<9>), grid, block, 0, static_cast<hipStream_t>(stream), h, args->members, args->episodes_stride);
+  HIP_TRY(hipGetLastError());
+  return ARMENV_OK;
+}
+
+int armenv_her_pop_sample_shared(int32_t device, const ArmEnvHerPopSharedArgs *args, void *stream) {
+  STORE_REFUSE(her_refusal(args ? &args->pop.one : nullptr, args ? &args->pop : nullptr));
+  STORE_REFUSE(args->share_ratio >= 0.0 && args->share_ratio <= 1.0 ? nullptr : "share_ratio outside [0,1]");
+  const ArmEnvHerArgs *a = &args->pop.one;
+  if (a->batch == 0) return ARMENV_OK;
+  DEV_ENTER(device);
+  const HerArgs h = her_args(a);
+  const dim3 grid(grid_for(a->batch, 256), args->pop.members), block(256);
+  if (a->obs_dim == 6)
+    hipLaunchKernelGGL((her_sample_pop_shared_kernel<6>), grid, block, 0, static_cast<hipStream_t>(stream), h, args->pop.members,
+                       args->pop.episodes_stride, args->share_ratio);
+  else
+    hipLaunchKernelGGL((her_sample_pop_shared_kernel<9>), grid, block, 0, static_cast<hipStream_t>(stream), h, args->pop.members,
+                       args->pop.episodes_stride, args->share_ratio);
   HIP_TRY(hipGetLastError());
   return ARMENV_OK;
 }

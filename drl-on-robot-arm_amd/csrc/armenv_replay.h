@@ -81,34 +81,20 @@ struct HerArgs {
   int32_t *picks_out;        // nullable
 };
 
-// sample b of the batch: the one body of her_sample_kernel and her_sample_pop_kernel
+// row b of a batch with nothing to sample from: defined and inert (zeros, done = 1); the picks are the caller's to write
 template <int D>
-AE_DEV void her_sample_one(const HerArgs &A, int64_t b) {
-  const int64_t E = *A.num_episodes;
-  int32_t ep, st, her, sg;
-  if (A.picks_in) {
-    ep = A.picks_in[4 * b]; st = A.picks_in[4 * b + 1]; her = A.picks_in[4 * b + 2]; sg = A.picks_in[4 * b + 3];
-  } else {
-    if (E <= 0) {   // nothing to sample from: a defined, inert batch
-      for (int k = 0; k < D; ++k) { A.states[b * D + k] = 0.f; A.next_states[b * D + k] = 0.f; }
-      A.actions[3 * b] = A.actions[3 * b + 1] = A.actions[3 * b + 2] = 0.f;
-      A.rewards[b] = 0.f;
-      A.dones[b] = 1;
-      if (A.picks_out) { A.picks_out[4 * b] = -1; A.picks_out[4 * b + 1] = A.picks_out[4 * b + 2] = A.picks_out[4 * b + 3] = 0; }
-      return;
-    }
-    double u0, u1, u2, u3;
-    // the sampler's own Philox key: with the env's key, (batch slot b, draw d) would read exactly the uniforms that chose the
-    // goal of env b in episode d whenever a caller seeds both with the same number (armenv.train does)
-    const uint64_t key = A.seed ^ 0x5DEECE66D1CE4E5Bull;
-    philox_pair(key, (uint64_t)b, (uint32_t)A.draw, 0u, u0, u1);
-    philox_pair(key, (uint64_t)b, (uint32_t)A.draw, 1u, u2, u3);
-    ep = (int32_t)(u0 * (double)E);                         // random.sample(buffer, 1)      rl_utils.py:126
-    const int32_t L = A.episodes[3 * ep + 2];
-    st = (int32_t)(u1 * (double)L);                         // np.random.randint(length)     :127
-    her = (A.use_her && u2 <= A.her_ratio) ? 1 : 0; // np.random.uniform() <= ratio  :134
-    sg = st + 1 + (int32_t)(u3 * (double)(L - st));         // randint(step+1, length+1)     :135
-  }
+AE_DEV void her_inert_row(const HerArgs &A, int64_t b) {
+  for (int k = 0; k < D; ++k) { A.states[b * D + k] = 0.f; A.next_states[b * D + k] = 0.f; }
+  A.actions[3 * b] = A.actions[3 * b + 1] = A.actions[3 * b + 2] = 0.f;
+  A.rewards[b] = 0.f;
+  A.dones[b] = 1;
+}
+
+// Row b of a batch from the pick (episode, step_state, use_her, step_goal): the transition, gathered from A's rings through A's
+// episode list and relabelled, written to row b of A's outputs.  The one gather of every sampler kernel; the picks are the caller's
+// to write.
+template <int D>
+AE_DEV void her_row(const HerArgs &A, int64_t b, int32_t ep, int32_t st, int32_t her, int32_t sg) {
   const int32_t *e = A.episodes + 3 * ep;
   const int64_t n = e[0], t0 = e[1];
   auto row = [&](int64_t lt) { return (A.ring_base + lt) % A.ring_cap; };   // logical step -> physical row
@@ -149,6 +135,40 @@ AE_DEV void her_sample_one(const HerArgs &A, int64_t b) {
   A.actions[3 * b] = a[0]; A.actions[3 * b + 1] = a[1]; A.actions[3 * b + 2] = a[2];
   A.rewards[b] = r;
   A.dones[b] = dn;
+}
+
+// The sampler's own Philox key: with the env's key, (batch slot b, draw d) would read exactly the uniforms that chose the goal of
+// env b in episode d whenever a caller seeds both with the same number (armenv.train does)
+constexpr uint64_t HER_KEY_XOR = 0x5DEECE66D1CE4E5Bull;
+
+// (step_state, use_her, step_goal) of a pick inside an episode of L steps, from the uniforms u1..u3 of its row
+AE_DEV void her_draw_steps(const HerArgs &A, int32_t L, double u1, double u2, double u3, int32_t &st, int32_t &her, int32_t &sg) {
+  st = (int32_t)(u1 * (double)L);                           // np.random.randint(length)     rl_utils.py:127
+  her = (A.use_her && u2 <= A.her_ratio) ? 1 : 0;           // np.random.uniform() <= ratio  :134
+  sg = st + 1 + (int32_t)(u3 * (double)(L - st));           // randint(step+1, length+1)     :135
+}
+
+// sample b of the batch: the one body of her_sample_kernel and her_sample_pop_kernel
+template <int D>
+AE_DEV void her_sample_one(const HerArgs &A, int64_t b) {
+  const int64_t E = *A.num_episodes;
+  int32_t ep, st, her, sg;
+  if (A.picks_in) {
+    ep = A.picks_in[4 * b]; st = A.picks_in[4 * b + 1]; her = A.picks_in[4 * b + 2]; sg = A.picks_in[4 * b + 3];
+  } else {
+    if (E <= 0) {   // nothing to sample from: a defined, inert batch
+      her_inert_row<D>(A, b);
+      if (A.picks_out) { A.picks_out[4 * b] = -1; A.picks_out[4 * b + 1] = A.picks_out[4 * b + 2] = A.picks_out[4 * b + 3] = 0; }
+      return;
+    }
+    double u0, u1, u2, u3;
+    const uint64_t key = A.seed ^ HER_KEY_XOR;
+    philox_pair(key, (uint64_t)b, (uint32_t)A.draw, 0u, u0, u1);
+    philox_pair(key, (uint64_t)b, (uint32_t)A.draw, 1u, u2, u3);
+    ep = (int32_t)(u0 * (double)E);                         // random.sample(buffer, 1)      rl_utils.py:126
+    her_draw_steps(A, A.episodes[3 * ep + 2], u1, u2, u3, st, her, sg);
+  }
+  her_row<D>(A, b, ep, st, her, sg);
   if (A.picks_out) { A.picks_out[4 * b] = ep; A.picks_out[4 * b + 1] = st; A.picks_out[4 * b + 2] = her; A.picks_out[4 * b + 3] = sg; }
 }
 
@@ -178,6 +198,74 @@ __global__ __launch_bounds__(256) void her_sample_pop_kernel(HerArgs A, int32_t 
   if (A.picks_out) A.picks_out += out * 4;
   A.seed += (uint64_t)p;
   her_sample_one<D>(A, b);
+}
+
+// The population form with a shared pool: her_sample_pop_kernel's grid and arrays, but a row of member p's batch may come from ANY
+// member's trajectories.  Member p draws u0..u3 as her_sample_pop_kernel does (key (seed + p) ^ HER_KEY_XOR, counter blocks 0 and
+// 1) and u4 from counter block 2 (words 0, 1; words 2, 3 are reserved and unread); the row is shared when u4 < share_ratio.
+//   not shared: source member m = p, episode (int32)(u0 E_p) -- her_sample_pop_kernel's row
+//   shared:     g = (int64)(u0 E_tot), E_tot = sum of num_episodes; m = the smallest member with g < E_0 + ... + E_m, episode
+//               g - (E_0 + ... + E_(m-1)) -- random.sample(buffer, 1) over the concatenation of the members' trajectory lists,
+//               which is her_sample_kernel's row on the members' rings merged column-wise ([cap][P N][...]) with seed + p
+// The step, the relabel flag and the goal step come from u1..u3 and the length of member m's episode; the transition is read from
+// member m's rings, the row is written into member p's outputs.  An empty pool (E_tot shared, E_p not) gives the inert row.
+// Picks in and out are [P][B][5] = (member, episode within it, step_state, use_her, step_goal), the inert row's (-1, -1, 0, 0, 0);
+// with picks supplied nothing is drawn, and a pick that names no member or none of its episodes gives the inert row.
+template <int D>
+__global__ __launch_bounds__(256) void her_sample_pop_shared_kernel(HerArgs A, int32_t members, int64_t episodes_stride,
+                                                                   double share_ratio) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t p = blockIdx.y;
+  if (b >= A.B || p >= members) return;
+  const int64_t *counts = A.num_episodes;                   // i64 [P]
+  const int64_t out = p * A.B;
+  A.states += out * D; A.next_states += out * D; A.actions += out * 3; A.rewards += out; A.dones += out;
+  int32_t *picks_out = A.picks_out ? A.picks_out + (out + b) * 5 : nullptr;
+  int32_t m = -1, ep = -1, st = 0, her = 0, sg = 0;
+  double u1 = 0.0, u2 = 0.0, u3 = 0.0;
+  if (A.picks_in) {
+    const int32_t *pk = A.picks_in + (out + b) * 5;
+    m = pk[0]; ep = pk[1]; st = pk[2]; her = pk[3]; sg = pk[4];
+    if (m < 0 || m >= members || ep < 0 || (int64_t)ep >= counts[m]) m = -1;
+  } else {
+    double u0, u4 = 1.0, unread;
+    const uint64_t key = (A.seed + (uint64_t)p) ^ HER_KEY_XOR;
+    philox_pair(key, (uint64_t)b, (uint32_t)A.draw, 0u, u0, u1);
+    philox_pair(key, (uint64_t)b, (uint32_t)A.draw, 1u, u2, u3);
+    if (share_ratio > 0.0) philox_pair(key, (uint64_t)b, (uint32_t)A.draw, 2u, u4, unread);   // else: u4 < 0 never holds
+    if (u4 < share_ratio) {
+      int64_t total = 0;
+      for (int32_t j = 0; j < members; ++j) total += counts[j] > 0 ? counts[j] : 0;
+      if (total > 0) {
+        const int64_t g = (int64_t)(u0 * (double)total);    // < total: u0 <= 1 - 2^-53 and total < 2^31
+        int64_t before = 0;                                 // E_0 + ... + E_(m-1)
+        for (int32_t j = 0; j < members; ++j) {
+          const int64_t Ej = counts[j];
+          if (Ej <= 0) continue;                            // an empty member is passed over
+          if (m >= 0) before += counts[m];
+          m = j;
+          if (g < before + Ej) break;
+        }
+        const int64_t within = g - before;
+        ep = (int32_t)(within < counts[m] ? within : counts[m] - 1);
+      }
+    } else if (counts[p] > 0) {
+      m = (int32_t)p;
+      ep = (int32_t)(u0 * (double)counts[p]);
+    }
+  }
+  if (m < 0) {
+    her_inert_row<D>(A, b);
+    if (picks_out) { picks_out[0] = picks_out[1] = -1; picks_out[2] = picks_out[3] = picks_out[4] = 0; }
+    return;
+  }
+  const int64_t ring = (int64_t)m * A.ring_cap * A.N;       // the source: member m's rings and episode list
+  A.obs0 += (int64_t)m * A.N * D;
+  A.obs_after += ring * D; A.next_obs += ring * D; A.action += ring * 3; A.reward += ring; A.done += ring;
+  A.episodes += (int64_t)m * episodes_stride * 3;
+  if (!A.picks_in) her_draw_steps(A, A.episodes[3 * ep + 2], u1, u2, u3, st, her, sg);
+  her_row<D>(A, b, ep, st, her, sg);
+  if (picks_out) { picks_out[0] = m; picks_out[1] = ep; picks_out[2] = st; picks_out[3] = her; picks_out[4] = sg; }
 }
 
 }  // namespace armenv

@@ -37,6 +37,7 @@ extern "C" {
 #define ARMENV_NJ 7
 #define ARMENV_ABI_VERSION 9   /* 9: ArmEnvHerArgs.her_ratio and .dis_threshold are double (were float): the sampler compares against the
                                      caller's own doubles, as the reference compares against Python floats; the struct grew by 8 bytes;
+                                     still 9: + armenv_her_pop_sample_shared and ArmEnvHerPopSharedArgs, additive in the same way;
                                   8: + armenv_daddpg_update, armenv_daddpg_workspace_bytes, ArmEnvDaddpgArgs;
                                      still 8: + armenv_datd3_update, armenv_datd3_workspace_bytes, ArmEnvDatd3Args -- purely additive
                                      (two functions, one struct, nothing existing moves), so the number did not change;
@@ -490,6 +491,37 @@ typedef struct ArmEnvHerPopArgs {
  * Refused: NULL args, members outside 1..64, episodes_stride < 1 and everything armenv_her_sample refuses (obs_dim, sizes, NULL
  * buffers, her_ratio).  batch == 0: ARMENV_OK, nothing is launched. */
 int armenv_her_pop_sample(int32_t device, const ArmEnvHerPopArgs *args, void *stream);
+
+typedef struct ArmEnvHerPopSharedArgs {
+  ArmEnvHerPopArgs pop;   /* as armenv_her_pop_sample; picks in and out are [P][B][5] */
+  double share_ratio;     /* in [0, 1]: the probability that a row is drawn from all members' trajectories */
+} ArmEnvHerPopSharedArgs;
+
+/* armenv_her_pop_sample with a shared pool: a row of member p's batch may come from ANY member's trajectories (the shared replay
+ * buffer of off-policy population training), still one launch (grid: ceil(B / 256) blocks x P members), no LDS, no scratch.
+ * The draw rule of row b of member p:
+ *   u0..u3 as armenv_her_pop_sample draws them: Philox key (seed + p) ^ 0x5DEECE66D1CE4E5B, counters (b lo, b hi, the low 32 bits
+ *   of draw, 0 | 1); u4 = the u53 of words (0, 1) of one more block, fourth counter word 2 (its words (2, 3) are reserved, unread).
+ *   shared = u4 < share_ratio, a strict compare against the caller's double: 0.0 never shares, 1.0 always does.
+ *   not shared: source member m = p, episode = (int32)(u0 E_p), as armenv_her_pop_sample.
+ *   shared:     E_tot = the sum of num_episodes, g = (int64)(u0 E_tot); m = the smallest member with g < E_0 + ... + E_m (members
+ *               without episodes are passed over), episode = g - (E_0 + ... + E_(m-1)): the reference's random.sample(buffer, 1)
+ *               over the concatenation of all members' trajectory lists.
+ *   step_state, use_her and step_goal come from u1..u3 and the length of member m's episode as ever; the transition and the HER
+ *   goal are read from member m's rings and obs0; the row is written into member p's output slices.
+ *   The pool is E_tot for a shared row and E_p otherwise; from an empty pool the row is the inert one (zeros, done = 1).
+ * Picks, in and out, are i32 [P][B][5] = (member, episode within that member, step_state, use_her, step_goal); the inert row's
+ * are (-1, -1, 0, 0, 0).  With picks supplied nothing is drawn; a pick whose member is outside 0..P-1 or whose episode is outside
+ * that member's list gives the inert row.
+ * Contracts, bit for bit: share_ratio = 0 leaves the bytes of armenv_her_pop_sample (picks: p in front of that call's four);
+ * share_ratio = 1 leaves in member p's slices the bytes of armenv_her_sample, seed + p and the same draw, on the members' rings
+ * merged column-wise -- [ring_cap][P N][...], column m N + n = member m's column n, obs0 [P N][D] -- and indexed by
+ * armenv_count_episodes / armenv_write_episodes (that index lists the episodes env-major: member after member), its pick's episode
+ * being this call's episode + E_0 + ... + E_(m-1).
+ * The total number of indexed episodes, E_tot, must stay below 2^31.
+ * Refused (ARMENV_EINVAL, the field named, before any HIP call): NULL args, everything armenv_her_pop_sample refuses, a share_ratio
+ * that is NaN or outside [0, 1].  batch == 0: ARMENV_OK, nothing is launched. */
+int armenv_her_pop_sample_shared(int32_t device, const ArmEnvHerPopSharedArgs *args, void *stream);
 
 /* ---- fused TD3 learner: one TD3_MLP.train update (the reference's algo/TD3/TD3_mlp.py:114-161) over the networks of
  * net_mlp.py:29-71 (actor: fc1-3, tanh x action_bound; twin critic over cat(s, a): fc1-3 = Q1, fc4-6 = Q2), hidden_dim 256:
